@@ -7,8 +7,19 @@ Workload at every N: HDenseFormer_32(in=4, n_cls=4, 128^3, transformer_depth=24)
 bf16 storage / fp32 accumulate (BASELINE configs[1]; configs[2] is the same at N=8).  Weak scaling.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what the headline figure does
+not need (N = 1 only): the roofline leg (the dominant conv launch bracketed inside the timed steps, then the conv family
+and that launch replayed back to back) and the bounded CPU baseline in a child process.  --dump-outputs DIR writes what
+the last timed step computed (loss, the four deep-supervision logits, the gradients and the parameters after the Adam
+step) as DIR/<name>.npy.  In such a run the last timed step starts again from the seeded initial weights and a fresh
+optimizer state, so its inputs (data, weights, dropout masks) depend only on the arguments: some gradient sums of a step
+are float atomics (the transformer's biases and LayerNorm parameters, the patch-embedding bias, the heads), the weights of
+two runs part by rounding after the first step and the bf16 storage amplifies that from step to step.  From the same
+inputs the logits and the loss repeat bit for bit, the gradients and updated weights to rounding (~2e-7).
 
 Prints ONE JSON line on rank 0 (plus human-readable notes on stderr)."""
 import argparse
@@ -279,6 +290,31 @@ def roofline_dominant_kernel(dev):
             "avg_launch_ms": ms, "flops_per_launch": flops, "algorithmic_bytes_per_launch": 2.0 * n * s ** 3 * (cin + cout)}
 
 
+def dump_outputs(path, loss, outs, net):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the four deep-supervision logits, every
+    parameter's gradient and every parameter after the Adam step (those two concatenated in named_parameters() order) --
+    as DIR/<name>.npy in float32 (the loss in float64).  An array above its cap is cut to a fixed sample of positions,
+    seeded by its length only, so two runs or two builds give the same positions: 41 MB at the default shape, at most
+    57 MB at any batch."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, t, cap):
+        v = t.detach().float().cpu().numpy()
+        if v.size > cap:
+            idx = np.sort(np.random.default_rng(v.size).choice(v.size, cap, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), v)
+
+    np.save(os.path.join(path, "loss.npy"), np.float64(loss.item()))
+    for i, o in enumerate(outs):
+        save(f"logits{i}", o, 1 << 21)
+    params = list(net.parameters())
+    save("grads", torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).flatten() for p in params]), 3 << 20)
+    save("params", torch.cat([p.detach().flatten() for p in params]), 3 << 20)
+    log(f"dump-outputs: loss, logits0-3, grads, params -> {path}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -286,9 +322,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=2, help="per-GPU batch")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline leg and the CPU baseline (N = 1); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, logits, gradients and updated parameters as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="skip the 120 launches of the roofline leg (per-kernel counter passes of tools/profile_round.sh)")
+                    help="with --full: skip the 120 launches of the roofline leg (per-kernel counter passes of "
+                         "tools/profile_round.sh)")
     ap.add_argument("--roofline-only", action="store_true",
                     help="only the roofline leg (the dominant kernel's timed launches): the command profiled for "
                          "profiles/*_roofline_kernel_stats.csv, whose per-kernel average must match avg_launch_ms")
@@ -351,6 +392,8 @@ def main():
     net.compute_dtype = a.dtype
     crit = DeepSuperloss(criterion=CEPlusDice(weight=None, ignore_index=0))
     opt = FlatAdam(net, lr=1e-3, weight_decay=1e-4)
+    # --dump-outputs: the seeded initial weights, restored before the last timed step (module docstring)
+    init_params = net.flat_parameters().detach().clone() if a.dump_outputs is not None else None
     sync = None
     if dist_on:
         from hdf_rt.parallel import GradSync
@@ -362,7 +405,9 @@ def main():
     lab = torch.randint(0, 4, (a.batch, 128, 128, 128), generator=g)
     target = torch.nn.functional.one_hot(lab, 4).permute(0, 4, 1, 2, 3).float().contiguous().to(dev)
 
-    def step():
+    kept = []          # the logits of the last timed step, for --dump-outputs
+
+    def step(keep=False):
         opt.zero_grad()
         outs = net(x)
         loss = crit(outs, target)
@@ -370,7 +415,16 @@ def main():
         if sync is not None:
             sync.wait()
         opt.step()
+        if keep:
+            kept[:] = outs
         return loss
+
+    def restart():
+        with torch.no_grad():
+            net.flat_parameters().copy_(init_params)
+            opt.exp_avg.zero_()
+            opt.exp_avg_sq.zero_()
+        opt.step_count = 0
 
     def fence():
         if dist_on:
@@ -385,8 +439,9 @@ def main():
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
     # the dominant conv launch INSIDE the timed steps: the library records one event pair per step around it
     # (hdf_plan_set_probe); read back after the closing fence
+    roofline = world == 1 and a.full and not a.no_roofline
     probes, plan_h = [], None
-    if world == 1 and not a.no_roofline:
+    if roofline:
         from hdf_rt._lib import check as _check, lib as _lib
         plan_h = net._last_rt.plan.h
         for _ in range(a.steps):
@@ -399,7 +454,10 @@ def main():
     for k in range(a.steps):
         if probes:
             _check(_lib().hdf_plan_set_probe(plan_h, probes[k][0].cuda_event, probes[k][1].cuda_event), "set_probe")
-        loss = step()
+        last = a.dump_outputs is not None and k == a.steps - 1
+        if last and opt.step_count:
+            restart()
+        loss = step(keep=last)
         evs[k + 1].record()
     t_enqueued = time.perf_counter() - t0          # host side only: all K steps issued (the GPU is still working)
     fence()
@@ -435,7 +493,9 @@ def main():
                                       "all": [round(v, 3) for v in raw_steps]},
             "host_issue_ms_per_step": t_enqueued / a.steps * 1e3,
         }
-        if world == 1 and not a.no_roofline:
+        if a.dump_outputs is not None:
+            dump_outputs(a.dump_outputs, loss, kept, net)
+        if roofline:
             wr = roofline_dominant_kernel(dev)
             rec["roofline"] = roofline_conv_family(dev)
             rec["roofline"]["step"], why = step_roofline_from_profile()
@@ -463,7 +523,7 @@ def main():
                     "avg_launch_ms": ms_in, "median_ms": in_step_ms[len(in_step_ms) // 2], "min_ms": in_step_ms[0],
                     "max_ms": in_step_ms[-1], "launches": len(in_step_ms),
                     "achieved": fl / (ms_in * 1e-3) / 1e12, "frac": fl / (ms_in * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS}
-        if world == 1:
+        if world == 1 and a.full:
             if not a.no_cpu_baseline:
                 del net, opt
                 torch.cuda.empty_cache()

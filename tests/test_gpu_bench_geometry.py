@@ -164,10 +164,16 @@ def _check_adam_vs_fixture(g, net, min_live=5000):
 def _grads_vs_oracle(net, sd, x, onehot, seed, tol, tight=()):
     tr = orc.OracleTrainer(sd)
     ref_loss, ref_outs = tr.loss_and_grads(x, onehot, None if seed < 0 else seed)
+    total = sum(float(v.grad.double().norm()) ** 2 for v in tr.sd.values()) ** 0.5
     errs = []
     for name, p in net.named_parameters():
         rg = tr.sd[name].grad
-        if rg.norm() < 1e-6:
+        # dead parameters.  An UpConv's conv bias (double_conv.0.bias) feeds an InstanceNorm without affine, which
+        # subtracts it again: its gradient is identically zero, the library leaves it at zero, and the oracle's fp32 sum
+        # over the voxels is rounding noise that grows with the volume and the host's reduction order (up3 at 160^3:
+        # 8.6e-7 on one host, above 1e-6 on another; the smallest live gradient there is 1.9e-4 of a total 3.0)
+        if rg.norm() < 1e-6 or name.endswith("double_conv.0.bias"):
+            assert float(rg.norm()) < 1e-5 * total, (name, float(rg.norm()), total)
             assert p.grad.norm().item() < 1e-4, name
             continue
         errs.append((name, _rl2(p.grad, rg)))

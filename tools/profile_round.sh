@@ -13,9 +13,9 @@ cd /tmp && export TMPDIR=/tmp
 PY=python3
 # 1. kernel trace + stats of the bench command (3 timed steps): the build as it ships (three streams in a step), then
 #    the SAME build with both stream knobs set (one stream: clean per-kernel durations), and the roofline leg alone
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- $PY $REPO/bench.py --steps 3 --warmup 2 --no-cpu-baseline > $OUT/bench_line_profiled.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- $PY $REPO/bench.py --steps 3 --warmup 2 --full --no-cpu-baseline > $OUT/bench_line_profiled.json 2> /dev/null
 export HDF_NO_ASYNC_WGRAD=1 HDF_NO_BRANCH_OVERLAP=1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench1s -- $PY $REPO/bench.py --steps 3 --warmup 2 --no-cpu-baseline > $OUT/bench1s_line_profiled.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench1s -- $PY $REPO/bench.py --steps 3 --warmup 2 --full --no-cpu-baseline > $OUT/bench1s_line_profiled.json 2> /dev/null
 unset HDF_NO_ASYNC_WGRAD HDF_NO_BRANCH_OVERLAP
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/roofline -- $PY $REPO/bench.py --roofline-only > $OUT/roofline_line.json 2> /dev/null
 # 2. HBM traffic of the dominant kernel: FETCH_SIZE and WRITE_SIZE in separate passes
@@ -40,5 +40,5 @@ unset HDF_NO_ASYNC_WGRAD HDF_NO_BRANCH_OVERLAP
 $PY $REPO/tools/clock_probe.py 64 32 > $OUT/clock_probe_64x32.txt 2>&1
 $PY $REPO/tools/clock_probe.py 32 32 > $OUT/clock_probe_32x32.txt 2>&1
 # 6. the un-profiled bench line
-$PY $REPO/bench.py --steps 20 --warmup 5 > $OUT/bench_line_full.json 2> $OUT/bench_line_full.err
+$PY $REPO/bench.py --steps 20 --warmup 5 --full > $OUT/bench_line_full.json 2> $OUT/bench_line_full.err
 find $OUT -name "*.csv" | head -50
