@@ -15,6 +15,14 @@ int hdf_launch_loss_fwd(int dtype, const void* const* logits, const float* targe
 int hdf_launch_loss_bwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
                         int H, int W, const float* ws, const float* grad_out, void* const* dlogits, hipStream_t st,
                         float w_ce = 1.f, float w_dice = 1.f, const float* class_weight = nullptr, int dice_ignore = 0);
+// focal forms (FocalLoss / FLPlusDice): w_focal * focal + w_dice * Dice per scale; reduction 0 sum, 1 mean
+int hdf_launch_loss_focal_fwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
+                              int H, int W, float* ws, float* loss_out, hipStream_t st, float w_focal, float alpha,
+                              float gamma, int reduction, float w_dice, const float* class_weight, int dice_ignore);
+int hdf_launch_loss_focal_bwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
+                              int H, int W, const float* ws, const float* grad_out, void* const* dlogits,
+                              hipStream_t st, float w_focal, float alpha, float gamma, int reduction, float w_dice,
+                              const float* class_weight, int dice_ignore);
 int hdf_launch_dice_counts(int dtype, const void* logits, const float* target, int N, int C, int64_t V,
                            unsigned long long* counts, hipStream_t st);
 int hdf_launch_confusion(int dtype, const void* logits, const float* target, int N, int C, int64_t V,

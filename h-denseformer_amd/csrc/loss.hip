@@ -1,10 +1,11 @@
-// Fused DeepSuperloss(CEPlusDice) forward/backward, on-device Dice metric, flat Adam.
+// Fused DeepSuperloss(CEPlusDice) and DeepSuperloss(FocalLoss / FLPlusDice) forward/backward, on-device Dice metric,
+// flat Adam.
 //
-// Reference: loss/combine_loss.py:8-35,68-79 ; loss/dice_loss.py:5-87 ; loss/cross_entropy.py:8-22 ;
+// Reference: loss/combine_loss.py:8-79 ; loss/dice_loss.py:5-87 ; loss/cross_entropy.py:8-22,45-73 ;
 // metric trainer.py:891-945 ; optimizer torch.optim.Adam as built by trainer.py:793-840.
 // One pass per scale reads the logits once (NCDHW, coalesced along voxels) and the fp32 one-hot target
 // at the 2^i-strided positions (nearest down-sampling), producing per-(sample,class) sums
-// sum(p*t), sum(p), sum(t) and the CE sum; backward recomputes the softmax from the logits.
+// sum(p*t), sum(p), sum(t) and the CE (or focal) sum; backward recomputes the softmax from the logits.
 #include <type_traits>
 
 #include "loss.h"
@@ -58,9 +59,46 @@ __device__ __forceinline__ void ld_tgt(const float* p, int stride, float* t) {
   }
 }
 
-template <typename T, int VEC, int MC>
+// FocalLoss (loss/cross_entropy.py:45-73) per (voxel, class) on the fp32 softmax p, as torch evaluates it:
+// bce = F.binary_cross_entropy (both logs clamped at -100), p_t = p t + (1-p)(1-t), loss = alpha_t bce (1-p_t)^gamma with
+// alpha_t = alpha t + (1-alpha)(1-t) (no factor when alpha < 0).  log p is the log-softmax (torch's log of the rounded
+// p up to one rounding; p underflowing to 0 clamps at -100 in both), log(1-p) is taken of the rounded 1-p as in torch.
+// The focal forms have no CE term: their sum takes the CE slot of the partials.
+struct FocalP {
+  float alpha, gamma;  // gamma is 0 or >= 1 (the launcher checks)
+  int mean;            // reduction 'mean' (divide by N*C*V of the scale) or 'sum'
+};
+// torch's pow(Tensor, Scalar) evaluates the small integer exponents as products
+__device__ __forceinline__ float focal_pow(float x, float g) {
+  return g == 2.f ? x * x : g == 1.f ? x : g == 0.f ? 1.f : g == 3.f ? x * x * x : powf(x, g);
+}
+struct FocalEl {
+  float bce, q, a;  // BCE, 1 - p_t, alpha_t
+};
+__device__ __forceinline__ FocalEl focal_el(float logp, float p, float t, const FocalP& fp) {
+  FocalEl r;
+  r.bce = -(t * fmaxf(logp, -100.f) + (1.f - t) * fmaxf(__logf(1.f - p), -100.f));
+  r.q = 1.f - (p * t + (1.f - p) * (1.f - t));
+  r.a = fp.alpha >= 0.f ? fp.alpha * t + (1.f - fp.alpha) * (1.f - t) : 1.f;
+  return r;
+}
+__device__ __forceinline__ float focal_loss_el(float logp, float p, float t, const FocalP& fp) {
+  const FocalEl e = focal_el(logp, p, t, fp);
+  return e.a * (e.bce * focal_pow(e.q, fp.gamma));
+}
+// d loss / d p by torch's autograd: BCE's backward is (p - t) / max(p (1-p), 1e-12) (not the derivative of the clamped
+// logs), and pow's backward is 0 for gamma == 0
+__device__ __forceinline__ float focal_dp_el(float logp, float p, float t, const FocalP& fp) {
+  const FocalEl e = focal_el(logp, p, t, fp);
+  float d = focal_pow(e.q, fp.gamma) * ((p - t) / fmaxf((1.f - p) * p, 1e-12f));
+  if (fp.gamma != 0.f) d += e.bce * (fp.gamma * focal_pow(e.q, fp.gamma - 1.f)) * (1.f - 2.f * t);
+  return e.a * d;
+}
+
+template <typename T, int VEC, int MC, bool FOCAL>
 __device__ __forceinline__ void loss_fwd_body(const LossLevel& L, int bx, const float* __restrict__ target, int C, int D,
-                                              int H, int W, const float* __restrict__ cw, float* acc) {
+                                              int H, int W, const float* __restrict__ cw, const FocalP& fp,
+                                              float* acc) {
   const T* logits = reinterpret_cast<const T*>(L.logits);
   const int n = blockIdx.y, Ws = L.Ws, Hs = L.Hs, stride = L.stride;
   const int64_t V = (int64_t)L.Ds * Hs * Ws, Vf = (int64_t)D * H * W;
@@ -108,7 +146,9 @@ __device__ __forceinline__ void loss_fwd_body(const LossLevel& L, int bx, const 
           acc[c] += p * t[c][j];
           acc[MAXC + c] += p;
           acc[2 * MAXC + c] += t[c][j];
-          if (c == tc) {
+          if constexpr (FOCAL) {
+            acc[3 * MAXC] += focal_loss_el(lg[c][j] - lse, p, t[c][j], fp);
+          } else if (c == tc) {
             // torch CrossEntropyLoss(weight=w, reduction='mean'): sum_v w[t_v] * nll_v / sum_v w[t_v]
             const float wv = cw ? cw[c] : 1.f;
             acc[3 * MAXC] += cw ? wv * (lse - lg[c][j]) : lse - lg[c][j];
@@ -119,6 +159,9 @@ __device__ __forceinline__ void loss_fwd_body(const LossLevel& L, int bx, const 
   }
 }
 
+// The kernel bodies below are written out per kernel rather than shared through a device function: that keeps the
+// code objects of the CE/Dice kernels exactly what they were before the focal forms were added (a function boundary
+// changes their scheduling).
 template <typename T, int MC>  // MC: class slots held in registers (4 or 8)
 __global__ __launch_bounds__(256) void loss_fwd_kernel(LossLevels lv, const float* __restrict__ target, int C, int D,
                                                        int H, int W,
@@ -135,9 +178,39 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(LossLevels lv, const floa
 #pragma unroll
   for (int k = 0; k < NSTAT; k++) acc[k] = 0.f;
   if (L.vec == 4)
-    loss_fwd_body<T, 4, MC>(L, bx, target, C, D, H, W, cw, acc);
+    loss_fwd_body<T, 4, MC, false>(L, bx, target, C, D, H, W, cw, FocalP{}, acc);
   else
-    loss_fwd_body<T, 1, MC>(L, bx, target, C, D, H, W, cw, acc);
+    loss_fwd_body<T, 1, MC, false>(L, bx, target, C, D, H, W, cw, FocalP{}, acc);
+#pragma unroll
+  for (int k = 0; k < NSTAT; k++) acc[k] = wave_sum(acc[k]);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0)
+#pragma unroll
+    for (int k = 0; k < NSTAT; k++) red[wave][k] = acc[k];
+  __syncthreads();
+  if (threadIdx.x < NSTAT)
+    partials[(((int64_t)i * gridDim.y + blockIdx.y) * LOSS_BLOCKS + bx) * NSTAT + threadIdx.x] =
+        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+// the focal forms: the same sums with the focal sum in the CE slot (class weights act on the Dice term only, in the
+// finalize)
+template <typename T, int MC>
+__global__ __launch_bounds__(256) void focal_fwd_kernel(LossLevels lv, const float* __restrict__ target, int C, int D,
+                                                        int H, int W, FocalP fp, float* __restrict__ partials) {
+  __shared__ float red[4][NSTAT];
+  int i = 0;
+#pragma unroll
+  for (int k = 1; k < 4; k++)
+    if (k < lv.nscale && (int)blockIdx.x >= lv.L[k].blk0) i = k;
+  const LossLevel& L = lv.L[i];
+  const int bx = blockIdx.x - L.blk0;
+  float acc[NSTAT];
+#pragma unroll
+  for (int k = 0; k < NSTAT; k++) acc[k] = 0.f;
+  if (L.vec == 4)
+    loss_fwd_body<T, 4, MC, true>(L, bx, target, C, D, H, W, nullptr, fp, acc);
+  else
+    loss_fwd_body<T, 1, MC, true>(L, bx, target, C, D, H, W, nullptr, fp, acc);
 #pragma unroll
   for (int k = 0; k < NSTAT; k++) acc[k] = wave_sum(acc[k]);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -152,11 +225,13 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(LossLevels lv, const floa
 
 // grid = nscale*N blocks of 256 threads (one per partial slot): per-(scale, sample) loss term + the backward
 // coefficients coef[(i*N+n)*MAXC + c] = (A, B) of the Dice gradient; terms[i*N+n] is summed by loss_total_kernel
-__global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ partials, int nscale, int N, int C,
-                                                            LossScales sc, float smooth, float w_ce,
-                                                            float w_dice, const float* __restrict__ cw, int ignore,
-                                                            float* __restrict__ terms, float* __restrict__ coefA,
-                                                            float* __restrict__ coefB, float* __restrict__ wsum_out) {
+// FOCAL: the CE slot holds the focal sum, divided by N*C*V for focal_mean and taken as it is for 'sum'
+template <bool FOCAL>
+__device__ __forceinline__ void loss_finalize_block(const float* __restrict__ partials, int nscale, int N, int C,
+                                                    const LossScales& sc, float smooth, float w_ce, float w_dice,
+                                                    const float* __restrict__ cw, int ignore, int focal_mean,
+                                                    float* __restrict__ terms, float* __restrict__ coefA,
+                                                    float* __restrict__ coefB, float* __restrict__ wsum_out) {
   __shared__ double red[4][NSTAT];
   const int i = blockIdx.x / N, n = blockIdx.x % N, blocks = sc.blocks[i];
   const float* base = partials + ((int64_t)i * N + n) * LOSS_BLOCKS * NSTAT;
@@ -166,7 +241,7 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
   for (int b = threadIdx.x; b < blocks; b += 256)
 #pragma unroll
     for (int k = 0; k < NSTAT; k++) s[k] += (double)base[(int64_t)b * NSTAT + k];
-  if (cw) {  // weighted CE: the denominator is the weight sum over ALL samples of the scale (slot NSTAT-1 of every n)
+  if (!FOCAL && cw) {  // weighted CE: the denominator is the weight sum over ALL samples of the scale (slot NSTAT-1 of every n)
     double wall = 0.0;
     for (int m = 0; m < N; m++) {
       const float* bm = partials + ((int64_t)i * N + m) * LOSS_BLOCKS * NSTAT;
@@ -187,8 +262,13 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
     double t[NSTAT];
     for (int k = 0; k < NSTAT; k++) t[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
     double V = (double)sc.V[i];
-    double ce = cw ? t[3 * MAXC] / t[3 * MAXC + 1] : t[3 * MAXC] / (V * N);
-    if (n == 0) wsum_out[i] = cw ? (float)t[3 * MAXC + 1] : (float)(V * N);
+    double ce;
+    if constexpr (FOCAL) {
+      ce = focal_mean ? t[3 * MAXC] / (V * N * C) : t[3 * MAXC];
+    } else {
+      ce = cw ? t[3 * MAXC] / t[3 * MAXC + 1] : t[3 * MAXC] / (V * N);
+      if (n == 0) wsum_out[i] = cw ? (float)t[3 * MAXC + 1] : (float)(V * N);
+    }
     double dice = 0.0;
     for (int c = 0; c < C; c++) {
       float A = 0.f, B = 0.f;
@@ -208,6 +288,23 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
   }
 }
 
+__global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ partials, int nscale, int N, int C,
+                                                            LossScales sc, float smooth, float w_ce,
+                                                            float w_dice, const float* __restrict__ cw, int ignore,
+                                                            float* __restrict__ terms, float* __restrict__ coefA,
+                                                            float* __restrict__ coefB, float* __restrict__ wsum_out) {
+  loss_finalize_block<false>(partials, nscale, N, C, sc, smooth, w_ce, w_dice, cw, ignore, 0, terms, coefA, coefB,
+                             wsum_out);
+}
+__global__ __launch_bounds__(256) void focal_finalize_kernel(const float* __restrict__ partials, int nscale, int N, int C,
+                                                             LossScales sc, float smooth, float w_focal, int focal_mean,
+                                                             float w_dice, const float* __restrict__ cw, int ignore,
+                                                             float* __restrict__ terms, float* __restrict__ coefA,
+                                                             float* __restrict__ coefB) {
+  loss_finalize_block<true>(partials, nscale, N, C, sc, smooth, w_focal, w_dice, cw, ignore, focal_mean, terms, coefA,
+                            coefB, nullptr);
+}
+
 __global__ void loss_total_kernel(const float* __restrict__ terms, int count, float* __restrict__ loss_out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     double t = 0.0;
@@ -225,9 +322,9 @@ struct LossBwdP {
   int ignore;
 };
 
-template <typename T, int VEC, int MC>
+template <typename T, int VEC, int MC, bool FOCAL>
 __device__ __forceinline__ void loss_bwd_body(const LossLevel& L, int i, int bx, const float* __restrict__ target, int N,
-                                              int C, int D, int H, int W, const LossBwdP& q) {
+                                              int C, int D, int H, int W, const LossBwdP& q, const FocalP& fp) {
   const T* logits = reinterpret_cast<const T*>(L.logits);
   T* dlogits = reinterpret_cast<T*>(L.dlogits);
   const int n = blockIdx.y, Ws = L.Ws, Hs = L.Hs, stride = L.stride;
@@ -235,6 +332,8 @@ __device__ __forceinline__ void loss_bwd_body(const LossLevel& L, int i, int bx,
   const float g = (*q.gup) / (float)stride;   // scale weight 1 / 2^i (combine_loss.py:68-79)
   const float kce0 = q.cw ? q.w_ce * g / q.wsum[i] : q.w_ce * g / ((float)V * (float)N);
   const float kd = q.w_dice * g / ((float)(q.ignore >= 0 ? C - 1 : C) * (float)N);
+  // focal: w_focal times the scale weight, over N*C*V for 'mean' (loss.mean() of the reference)
+  const float kf = FOCAL ? (fp.mean ? q.w_ce * g / ((float)V * (float)N * (float)C) : q.w_ce * g) : 0.f;
   float cwr[MC], cA[MC], cB[MC];
 #pragma unroll
   for (int c = 0; c < MC; c++) {
@@ -278,22 +377,30 @@ __device__ __forceinline__ void loss_bwd_body(const LossLevel& L, int i, int bx,
           se += p[c];
         }
       float inv = 1.f / se, dot = 0.f, G[MC];
+      const float lse = FOCAL ? mx + __logf(se) : 0.f;
 #pragma unroll
       for (int c = 0; c < MC; c++)
         if (c < C) {
           p[c] *= inv;
           G[c] = -kd * (cA[c] * t[c][j] - cB[c]);  // dDice/dp_c (the coefficients of the ignored class are zero)
+          if constexpr (FOCAL) G[c] += kf * focal_dp_el(lg[c][j] - lse, p[c], t[c][j], fp);
           dot += G[c] * p[c];
         }
-      float kce = kce0;
-      if (q.cw) {
+      if constexpr (FOCAL) {  // both terms through the softmax backward p (G - <G, p>)
 #pragma unroll
         for (int c = 0; c < MC; c++)
-          if (c == tc) kce = kce0 * cwr[c];
-      }
+          if (c < C) lg[c][j] = p[c] * (G[c] - dot);
+      } else {
+        float kce = kce0;
+        if (q.cw) {
 #pragma unroll
-      for (int c = 0; c < MC; c++)
-        if (c < C) lg[c][j] = kce * (p[c] - (c == tc ? 1.f : 0.f)) + p[c] * (G[c] - dot);
+          for (int c = 0; c < MC; c++)
+            if (c == tc) kce = kce0 * cwr[c];
+        }
+#pragma unroll
+        for (int c = 0; c < MC; c++)
+          if (c < C) lg[c][j] = kce * (p[c] - (c == tc ? 1.f : 0.f)) + p[c] * (G[c] - dot);
+      }
     }
 #pragma unroll
     for (int c = 0; c < MC; c++)
@@ -311,9 +418,24 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(LossLevels lv, const floa
   const LossLevel& L = lv.L[i];
   const int bx = blockIdx.x - L.blk0;
   if (L.vec == 4)
-    loss_bwd_body<T, 4, MC>(L, i, bx, target, N, C, D, H, W, q);
+    loss_bwd_body<T, 4, MC, false>(L, i, bx, target, N, C, D, H, W, q, FocalP{});
   else
-    loss_bwd_body<T, 1, MC>(L, i, bx, target, N, C, D, H, W, q);
+    loss_bwd_body<T, 1, MC, false>(L, i, bx, target, N, C, D, H, W, q, FocalP{});
+}
+// q.w_ce carries w_focal and q.cw is null (the class weights are folded into the Dice coefficients by the finalize)
+template <typename T, int MC>
+__global__ __launch_bounds__(256) void focal_bwd_kernel(LossLevels lv, const float* __restrict__ target, int N, int C,
+                                                        int D, int H, int W, LossBwdP q, FocalP fp) {
+  int i = 0;
+#pragma unroll
+  for (int k = 1; k < 4; k++)
+    if (k < lv.nscale && (int)blockIdx.x >= lv.L[k].blk0) i = k;
+  const LossLevel& L = lv.L[i];
+  const int bx = blockIdx.x - L.blk0;
+  if (L.vec == 4)
+    loss_bwd_body<T, 4, MC, true>(L, i, bx, target, N, C, D, H, W, q, fp);
+  else
+    loss_bwd_body<T, 1, MC, true>(L, i, bx, target, N, C, D, H, W, q, fp);
 }
 
 // ---------------------------------------------------------------------------------- Dice metric
@@ -520,9 +642,10 @@ static int loss_levels(const void* const* logits, void* const* dlogits, const fl
   return HDF_OK;
 }
 
-int hdf_launch_loss_fwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
-                        int H, int W, float* ws, float* loss_out, hipStream_t st, float w_ce, float w_dice,
-                        const float* class_weight, int dice_ignore) {
+// fp == nullptr: the CE/Dice kernels (w_ce, class_weight of CEPlusDice); else the focal kernels with w_ce = w_focal
+static int launch_loss_fwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
+                           int H, int W, float* ws, float* loss_out, hipStream_t st, float w_ce, float w_dice,
+                           const float* class_weight, int dice_ignore, const FocalP* fp) {
   HDF_CHECK_ARG(C <= MAXC && C >= 2, "loss: n_cls=%d unsupported (2..%d)", C, MAXC);
   HDF_CHECK_ARG(dice_ignore >= -1 && dice_ignore < C, "loss: ignore_index %d outside [-1, %d)", dice_ignore, C);
   HDF_CHECK_ARG(nscale >= 1 && nscale <= 4 && nscale * N <= 256, "loss: nscale=%d N=%d", nscale, N);
@@ -534,7 +657,13 @@ int hdf_launch_loss_fwd(int dtype, const void* const* logits, const float* targe
   int blocks = 0;
   HDF_TRY(loss_levels(logits, nullptr, target, nscale, D, H, W, lv, sc, blocks));
   HDF_DISPATCH_T(dtype, {
-    if (C <= 4)
+    if (fp && C <= 4)
+      hipLaunchKernelGGL((focal_fwd_kernel<T, 4>), dim3(blocks, N), dim3(256), 0, st, lv, target, C, D, H, W, *fp,
+                         partials);
+    else if (fp)
+      hipLaunchKernelGGL((focal_fwd_kernel<T, MAXC>), dim3(blocks, N), dim3(256), 0, st, lv, target, C, D, H, W, *fp,
+                         partials);
+    else if (C <= 4)
       hipLaunchKernelGGL((loss_fwd_kernel<T, 4>), dim3(blocks, N), dim3(256), 0, st, lv, target, C, D, H, W, class_weight,
                          partials);
     else
@@ -544,35 +673,88 @@ int hdf_launch_loss_fwd(int dtype, const void* const* logits, const float* targe
   HDF_LAUNCH_CHECK();
   float* terms = coefB + (size_t)nscale * N * MAXC;
   float* wsum = terms + (size_t)nscale * N;  // [nscale]: denominator of the cross-entropy mean (the 16 spare floats)
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(nscale * N), dim3(256), 0, st, partials, nscale, N, C, sc, 1e-5f, w_ce,
-                     w_dice, class_weight, dice_ignore, terms, coefA, coefB, wsum);
+  if (fp)
+    hipLaunchKernelGGL(focal_finalize_kernel, dim3(nscale * N), dim3(256), 0, st, partials, nscale, N, C, sc, 1e-5f, w_ce,
+                       fp->mean, w_dice, class_weight, dice_ignore, terms, coefA, coefB);
+  else
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(nscale * N), dim3(256), 0, st, partials, nscale, N, C, sc, 1e-5f, w_ce,
+                       w_dice, class_weight, dice_ignore, terms, coefA, coefB, wsum);
   HDF_LAUNCH_CHECK();
   hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(64), 0, st, terms, nscale * N, loss_out);
   HDF_LAUNCH_CHECK();
   return HDF_OK;
 }
 
-int hdf_launch_loss_bwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
-                        int H, int W, const float* ws, const float* grad_out, void* const* dlogits, hipStream_t st,
-                        float w_ce, float w_dice, const float* class_weight, int dice_ignore) {
+static int launch_loss_bwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
+                           int H, int W, const float* ws, const float* grad_out, void* const* dlogits, hipStream_t st,
+                           float w_ce, float w_dice, const float* class_weight, int dice_ignore, const FocalP* fp) {
   HDF_CHECK_ARG(nscale >= 1 && nscale <= 4, "loss: nscale=%d", nscale);
   LossBwdP q;
   q.coefA = ws + (size_t)nscale * N * LOSS_BLOCKS * NSTAT;
   q.coefB = q.coefA + (size_t)nscale * N * MAXC;
   q.wsum = q.coefB + (size_t)nscale * N * MAXC + (size_t)nscale * N;
-  q.gup = grad_out, q.cw = class_weight, q.w_ce = w_ce, q.w_dice = w_dice, q.ignore = dice_ignore;
+  q.gup = grad_out, q.cw = fp ? nullptr : class_weight, q.w_ce = w_ce, q.w_dice = w_dice, q.ignore = dice_ignore;
   LossLevels lv;
   LossScales sc;
   int blocks = 0;
   HDF_TRY(loss_levels(logits, dlogits, target, nscale, D, H, W, lv, sc, blocks));
   HDF_DISPATCH_T(dtype, {
-    if (C <= 4)
+    if (fp && C <= 4)
+      hipLaunchKernelGGL((focal_bwd_kernel<T, 4>), dim3(blocks, N), dim3(256), 0, st, lv, target, N, C, D, H, W, q, *fp);
+    else if (fp)
+      hipLaunchKernelGGL((focal_bwd_kernel<T, MAXC>), dim3(blocks, N), dim3(256), 0, st, lv, target, N, C, D, H, W, q,
+                         *fp);
+    else if (C <= 4)
       hipLaunchKernelGGL((loss_bwd_kernel<T, 4>), dim3(blocks, N), dim3(256), 0, st, lv, target, N, C, D, H, W, q);
     else
       hipLaunchKernelGGL((loss_bwd_kernel<T, MAXC>), dim3(blocks, N), dim3(256), 0, st, lv, target, N, C, D, H, W, q);
   });
   HDF_LAUNCH_CHECK();
   return HDF_OK;
+}
+
+int hdf_launch_loss_fwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
+                        int H, int W, float* ws, float* loss_out, hipStream_t st, float w_ce, float w_dice,
+                        const float* class_weight, int dice_ignore) {
+  return launch_loss_fwd(dtype, logits, target, nscale, N, C, D, H, W, ws, loss_out, st, w_ce, w_dice, class_weight,
+                         dice_ignore, nullptr);
+}
+
+int hdf_launch_loss_bwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
+                        int H, int W, const float* ws, const float* grad_out, void* const* dlogits, hipStream_t st,
+                        float w_ce, float w_dice, const float* class_weight, int dice_ignore) {
+  return launch_loss_bwd(dtype, logits, target, nscale, N, C, D, H, W, ws, grad_out, dlogits, st, w_ce, w_dice,
+                         class_weight, dice_ignore, nullptr);
+}
+
+// gamma in (0, 1) is refused: the reference's pow backward gives NaN for a confidently right voxel there
+static int focal_params(int C, float alpha, float gamma, int reduction, FocalP& fp) {
+  HDF_CHECK_ARG(C <= MAXC && C >= 2, "focal loss: n_cls=%d unsupported (2..%d)", C, MAXC);
+  HDF_CHECK_ARG(gamma == 0.f || gamma >= 1.f, "focal loss: gamma=%g unsupported (0 or >= 1)", (double)gamma);
+  HDF_CHECK_ARG(alpha == alpha, "focal loss: alpha is NaN");
+  HDF_CHECK_ARG(reduction == 0 || reduction == 1, "focal loss: reduction %d (0 sum, 1 mean)", reduction);
+  fp.alpha = alpha, fp.gamma = gamma, fp.mean = reduction;
+  return HDF_OK;
+}
+
+int hdf_launch_loss_focal_fwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
+                              int H, int W, float* ws, float* loss_out, hipStream_t st, float w_focal, float alpha,
+                              float gamma, int reduction, float w_dice, const float* class_weight, int dice_ignore) {
+  FocalP fp;
+  HDF_TRY(focal_params(C, alpha, gamma, reduction, fp));
+  return launch_loss_fwd(dtype, logits, target, nscale, N, C, D, H, W, ws, loss_out, st, w_focal, w_dice, class_weight,
+                         dice_ignore, &fp);
+}
+
+int hdf_launch_loss_focal_bwd(int dtype, const void* const* logits, const float* target, int nscale, int N, int C, int D,
+                              int H, int W, const float* ws, const float* grad_out, void* const* dlogits,
+                              hipStream_t st, float w_focal, float alpha, float gamma, int reduction, float w_dice,
+                              const float* class_weight, int dice_ignore) {
+  FocalP fp;
+  HDF_TRY(focal_params(C, alpha, gamma, reduction, fp));
+  HDF_CHECK_ARG(dice_ignore >= -1 && dice_ignore < C, "loss: ignore_index %d outside [-1, %d)", dice_ignore, C);
+  return launch_loss_bwd(dtype, logits, target, nscale, N, C, D, H, W, ws, grad_out, dlogits, st, w_focal, w_dice,
+                         class_weight, dice_ignore, &fp);
 }
 
 int hdf_launch_dice_counts(int dtype, const void* logits, const float* target, int N, int C, int64_t V,

@@ -2258,6 +2258,28 @@ int hdf_loss_weighted_backward(int dtype, const void* out0, const void* out1, co
                              grad_out, douts, (hipStream_t)stream, ce_weight, dice_weight, class_weight,
                              dice_ignore_index);
 }
+int hdf_loss_focal_forward(int dtype, const void* out0, const void* out1, const void* out2, const void* out3, int nscale,
+                           const float* target_onehot, int batch, int n_cls, int D, int H, int W, float focal_weight,
+                           float focal_alpha, float focal_gamma, int focal_reduction, float dice_weight,
+                           const float* class_weight, int dice_ignore_index, void* workspace, float* loss_out,
+                           hdf_stream stream) {
+  const void* outs[4] = {out0, out1, out2, out3};
+  return hdf_launch_loss_focal_fwd(dtype, outs, target_onehot, nscale, batch, n_cls, D, H, W, (float*)workspace,
+                                   loss_out, (hipStream_t)stream, focal_weight, focal_alpha, focal_gamma,
+                                   focal_reduction, dice_weight, class_weight, dice_ignore_index);
+}
+int hdf_loss_focal_backward(int dtype, const void* out0, const void* out1, const void* out2, const void* out3,
+                            int nscale, const float* target_onehot, int batch, int n_cls, int D, int H, int W,
+                            float focal_weight, float focal_alpha, float focal_gamma, int focal_reduction,
+                            float dice_weight, const float* class_weight, int dice_ignore_index, const void* workspace,
+                            const float* grad_out, void* dout0, void* dout1, void* dout2, void* dout3,
+                            hdf_stream stream) {
+  const void* outs[4] = {out0, out1, out2, out3};
+  void* douts[4] = {dout0, dout1, dout2, dout3};
+  return hdf_launch_loss_focal_bwd(dtype, outs, target_onehot, nscale, batch, n_cls, D, H, W, (const float*)workspace,
+                                   grad_out, douts, (hipStream_t)stream, focal_weight, focal_alpha, focal_gamma,
+                                   focal_reduction, dice_weight, class_weight, dice_ignore_index);
+}
 int hdf_dice_counts(int dtype, const void* logits, const float* target_onehot, int batch, int n_cls, int64_t voxels,
                     uint64_t* counts, hdf_stream stream) {
   return hdf_launch_dice_counts(dtype, logits, target_onehot, batch, n_cls, voxels, (unsigned long long*)counts,

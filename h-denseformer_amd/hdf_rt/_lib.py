@@ -51,6 +51,10 @@ _PROTOS = {
                                        _vp]),
     "hdf_loss_weighted_backward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _vp, _vp,
                                         _vp, _vp, _vp, _vp, _vp]),
+    "hdf_loss_focal_forward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _i,
+                                    _vp, _vp, _vp]),
+    "hdf_loss_focal_backward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _i,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hdf_dice_counts": (_i, [_i, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "hdf_confusion_matrix": (_i, [_i, _vp, _vp, _i, _i, _i64, _vp, _i, _vp]),
     "hdf_confusion_matrix_labels": (_i, [_vp, _vp, _i, _i64, _vp, _i, _vp]),

@@ -1,5 +1,6 @@
-"""Fused DeepSuperloss(CEPlusDice) on the GPU: one autograd node, one pass over the logits per scale
-(hdf_loss_forward / hdf_loss_backward in include/hdf.h).  Reference: loss/combine_loss.py:8-35,68-79."""
+"""Fused DeepSuperloss(CEPlusDice) and DeepSuperloss(FocalLoss / FLPlusDice) on the GPU: one autograd node each, one
+pass over the logits per scale (hdf_loss_weighted_* / hdf_loss_focal_* in include/hdf.h).  Reference:
+loss/combine_loss.py:8-79, loss/cross_entropy.py:45-73."""
 import torch
 
 from . import _lib
@@ -26,6 +27,37 @@ def _device_class_weight(cw, device):
     return t
 
 
+def _inputs(target, outs):
+    """the checks every fused loss node makes: GPU tensors, one floating dtype, 1..4 scales of [B,C,D,H,W] or [B,C,H,W]
+    halving per scale.  Returns the contiguous logits, the fp32 target, B, C and (D, H, W) (D = 1 for 2-D logits)."""
+    if not all(o.is_cuda for o in outs) or not target.is_cuda:
+        raise _lib.HdfError("fused loss needs GPU tensors (no CPU fallback)")
+    dt = outs[0].dtype
+    if dt not in _DT or any(o.dtype != dt for o in outs):
+        raise _lib.HdfError(f"fused loss: logits must all be float32, all bfloat16 or all float16 (got {[o.dtype for o in outs]})")
+    n = len(outs)
+    if not 1 <= n <= 4:
+        raise _lib.HdfError("fused loss handles 1..4 deep-supervision scales")
+    if target.dim() not in (4, 5):
+        raise _lib.HdfError(f"fused loss: target must be [B,C,D,H,W] or [B,C,H,W], got {tuple(target.shape)}")
+    sp = tuple(target.shape[2:])
+    b, c = target.shape[:2]
+    dhw = ((1,) + sp) if len(sp) == 2 else sp        # 2-D logits (HDenseFormer_2D): depth 1
+    for i, o in enumerate(outs):
+        if tuple(o.shape) != (b, c) + tuple(v >> i for v in sp):
+            raise AssertionError(f"predict & target shape do not match at scale {i}: {tuple(o.shape)}")
+    return [o.contiguous() for o in outs], target.float().contiguous(), b, c, dhw
+
+
+def _dice_weight(cw, c, device):
+    if cw is None:
+        return None
+    cw = _device_class_weight(cw, device)
+    if cw.dim() != 1 or cw.shape[0] != c:
+        raise AssertionError(f"Expect weight shape [{c}], get[{tuple(cw.shape)}]")     # dice_loss.py:80-81
+    return cw
+
+
 class DeepSuperCEDice(torch.autograd.Function):
     """apply(target, *outs) = DeepSuperloss(CEPlusDice(weight=None, ignore_index=0)); apply((target, w_ce, w_dice), *outs)
     weights the two terms (0,1: DiceLoss(ignore_index=0); 1,0: CrossentropyLoss); apply((target, w_ce, w_dice,
@@ -40,28 +72,9 @@ class DeepSuperCEDice(torch.autograd.Function):
                 target, w_ce, w_dice = target
             else:
                 target, w_ce, w_dice, cw, ignore = target
-        if not all(o.is_cuda for o in outs) or not target.is_cuda:
-            raise _lib.HdfError("fused loss needs GPU tensors (no CPU fallback)")
-        dt = outs[0].dtype
-        if dt not in _DT or any(o.dtype != dt for o in outs):
-            raise _lib.HdfError(f"fused loss: logits must all be float32, all bfloat16 or all float16 (got {[o.dtype for o in outs]})")
-        n = len(outs)
-        if not 1 <= n <= 4:
-            raise _lib.HdfError("fused loss handles 1..4 deep-supervision scales")
-        if target.dim() not in (4, 5):
-            raise _lib.HdfError(f"fused loss: target must be [B,C,D,H,W] or [B,C,H,W], got {tuple(target.shape)}")
-        sp = tuple(target.shape[2:])
-        b, c = target.shape[:2]
-        d, h, w = ((1,) + sp) if len(sp) == 2 else sp        # 2-D logits (HDenseFormer_2D): depth 1
-        for i, o in enumerate(outs):
-            if tuple(o.shape) != (b, c) + tuple(v >> i for v in sp):
-                raise AssertionError(f"predict & target shape do not match at scale {i}: {tuple(o.shape)}")
-        outs = [o.contiguous() for o in outs]
-        tgt = target.float().contiguous()
-        if cw is not None:
-            cw = _device_class_weight(cw, tgt.device)
-            if cw.dim() != 1 or cw.shape[0] != c:
-                raise AssertionError(f"Expect weight shape [{c}], get[{tuple(cw.shape)}]")     # dice_loss.py:80-81
+        outs, tgt, b, c, (d, h, w) = _inputs(target, outs)
+        n, dt = len(outs), outs[0].dtype
+        cw = _dice_weight(cw, c, tgt.device)
         ign = -1 if ignore is None else int(ignore)
         ws = torch.empty(lib().hdf_loss_workspace_bytes(b), dtype=torch.uint8, device=tgt.device)
         loss = torch.empty((), dtype=torch.float32, device=tgt.device)
@@ -86,6 +99,66 @@ class DeepSuperCEDice(torch.autograd.Function):
         check(lib().hdf_loss_weighted_backward(_DT[outs[0].dtype], po[0], po[1], po[2], po[3], n, ptr(tgt), b, c, d, h,
                                                w, ctx.w[0], ctx.w[1], ptr(ctx.cw), ctx.ign, ptr(ws), ptr(gg), pd[0],
                                                pd[1], pd[2], pd[3], stream_ptr()), "hdf_loss_weighted_backward")
+        return (None, *douts)
+
+
+_REDUCTIONS = {"sum": 0, "mean": 1}
+
+
+def focal_settings(alpha, gamma, reduction):
+    """FocalLoss(alpha, gamma, reduction) settings the kernels implement (loss/cross_entropy.py:45-73), checked where the
+    module is built: reduction 'sum' or 'mean' (the reference's unreduced map cannot pass through DeepSuperloss), gamma 0
+    or >= 1 (in (0, 1) the reference's own gradient of a confidently right voxel is NaN), any alpha (< 0: no factor)."""
+    if reduction not in _REDUCTIONS:
+        raise NotImplementedError(f"fused FocalLoss implements reduction='sum' and 'mean' (got {reduction!r})")
+    a, g = float(alpha), float(gamma)
+    if not (g == 0.0 or g >= 1.0):
+        raise NotImplementedError(f"fused FocalLoss implements gamma == 0 or gamma >= 1 (got {gamma!r}: the reference's "
+                                  f"gradient is NaN there)")
+    if a != a:
+        raise NotImplementedError("fused FocalLoss: alpha is NaN")
+    return a, g, _REDUCTIONS[reduction]
+
+
+class DeepSuperFocalDice(torch.autograd.Function):
+    """apply((target, w_focal, alpha, gamma, reduction, w_dice, class_weight, ignore_index), *outs) =
+    sum_i 2^-i (w_focal * FocalLoss(alpha, gamma, reduction) + w_dice * DiceLoss(class_weight, ignore_index)) of scale i
+    (hdf_loss_focal_*).  FocalLoss is (target, 1, alpha, gamma, reduction, 0, None, 0); FLPlusDice(weight, ignore_index) is
+    (target, 1, 1, 2, 'mean', 1, weight, ignore_index); the class weight acts on the Dice term only.  The focal term is
+    evaluated in fp32 from the stored logits of any of the three dtypes (the reference raises on 16-bit logits with an
+    fp32 target)."""
+
+    @staticmethod
+    def forward(ctx, spec, *outs):
+        target, w_focal, alpha, gamma, reduction, w_dice, cw, ignore = spec
+        alpha, gamma, red = focal_settings(alpha, gamma, reduction)
+        outs, tgt, b, c, (d, h, w) = _inputs(target, outs)
+        n, dt = len(outs), outs[0].dtype
+        cw = _dice_weight(cw, c, tgt.device)
+        ign = -1 if ignore is None else int(ignore)
+        ws = torch.empty(lib().hdf_loss_workspace_bytes(b), dtype=torch.uint8, device=tgt.device)
+        loss = torch.empty((), dtype=torch.float32, device=tgt.device)
+        po = [ptr(o) for o in outs] + [None] * (4 - n)
+        args = (float(w_focal), alpha, gamma, red, float(w_dice), ptr(cw), ign)
+        check(lib().hdf_loss_focal_forward(_DT[dt], po[0], po[1], po[2], po[3], n, ptr(tgt), b, c, d, h, w, *args,
+                                           ptr(ws), ptr(loss), stream_ptr()), "hdf_loss_focal_forward")
+        ctx.save_for_backward(tgt, ws, *outs)
+        ctx.n, ctx.args, ctx.dhw, ctx.cw = n, args, (d, h, w), cw
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        tgt, ws, *outs = ctx.saved_tensors
+        n = ctx.n
+        b, c = tgt.shape[:2]
+        d, h, w = ctx.dhw
+        douts = [torch.empty_like(o) for o in outs]
+        gg = g.detach().float().reshape(1).contiguous()
+        po = [ptr(o) for o in outs] + [None] * (4 - n)
+        pd = [ptr(o) for o in douts] + [None] * (4 - n)
+        check(lib().hdf_loss_focal_backward(_DT[outs[0].dtype], po[0], po[1], po[2], po[3], n, ptr(tgt), b, c, d, h, w,
+                                            *ctx.args, ptr(ws), ptr(gg), pd[0], pd[1], pd[2], pd[3], stream_ptr()),
+              "hdf_loss_focal_backward")
         return (None, *douts)
 
 

@@ -186,6 +186,28 @@ int hdf_loss_weighted_backward(int dtype, const void* out0, const void* out1, co
                                float ce_weight, float dice_weight, const float* class_weight, int dice_ignore_index,
                                const void* workspace, const float* grad_out, void* dout0, void* dout1, void* dout2,
                                void* dout3, hdf_stream stream);
+/* the two-class losses: trainer.py:755-757 builds FocalLoss(reduction='sum') when config.py:127 picks it (NUM_CLASSES
+ * == 2, config.py:59), wrapped in DeepSuperloss (trainer.py:222-226, combine_loss.py:68-79).  Per scale
+ * focal_weight * Focal + dice_weight * Dice, with Focal of loss/cross_entropy.py:45-73 on the softmax p of the logits and
+ * the (soft, [0,1]) target t, per element alpha_t * BCE(p, t) * (1 - p_t)^gamma (BCE's logs clamped at -100, p_t =
+ * p t + (1-p)(1-t), alpha_t = alpha t + (1-alpha)(1-t), no alpha factor when alpha < 0), summed over all batch x n_cls x
+ * voxels (focal_reduction 0, 'sum') or averaged over them (1, 'mean'); gradients as torch's autograd (BCE backward
+ * (p - t) / max(p (1-p), 1e-12); the pow backward is 0 at gamma 0).  gamma must be 0 or >= 1 (in (0, 1) the reference's
+ * gradient is NaN for a confident right voxel).  The Dice term, class_weight and dice_ignore_index are those of
+ * hdf_loss_weighted_*; the class weight acts on the Dice term only.  FocalLoss(alpha, gamma, reduction=r) is
+ * (1, alpha, gamma, r, 0, NULL, 0); FLPlusDice(weight, ignore_index) (loss/combine_loss.py:37-64) is
+ * (1, 1, 2, 1, 1, weight, ignore_index).  Same workspace as hdf_loss_weighted_* (hdf_loss_workspace_bytes). */
+int hdf_loss_focal_forward(int dtype, const void* out0, const void* out1, const void* out2, const void* out3, int nscale,
+                           const float* target_onehot, int batch, int n_cls, int D, int H, int W, float focal_weight,
+                           float focal_alpha, float focal_gamma, int focal_reduction, float dice_weight,
+                           const float* class_weight, int dice_ignore_index, void* workspace, float* loss_out,
+                           hdf_stream stream);
+int hdf_loss_focal_backward(int dtype, const void* out0, const void* out1, const void* out2, const void* out3,
+                            int nscale, const float* target_onehot, int batch, int n_cls, int D, int H, int W,
+                            float focal_weight, float focal_alpha, float focal_gamma, int focal_reduction,
+                            float dice_weight, const float* class_weight, int dice_ignore_index, const void* workspace,
+                            const float* grad_out, void* dout0, void* dout1, void* dout2, void* dout3,
+                            hdf_stream stream);
 /* hard-argmax Dice counts of trainer.py:919-945: counts[batch][8][3] = (|P&T|, |P|, |T|) per class, uint64 */
 int hdf_dice_counts(int dtype, const void* logits, const float* target_onehot, int batch, int n_cls, int64_t voxels,
                     uint64_t* counts, hdf_stream stream);

@@ -179,5 +179,19 @@ try:
     ms = gpu_ms(step3, reps=3, warm=1)
     emit(row="8f-4 HDenseFormer_2D_32 train step, PI-CAI shape", config="batch 24 of 2x384^2, fwd + DeepSuper CE+Dice + bwd + Adam, bf16",
          gpu_ms=ms, samples_per_s=24 / ms * 1e3)
+    # the loss the reference trainer builds for this two-class workload (config.py:127, trainer.py:755-757)
+    from loss.cross_entropy import FocalLoss
+    crit_fl = DeepSuperloss(criterion=FocalLoss(reduction="sum"))
+
+    def step3_focal():
+        opt3.zero_grad()
+        loss = crit_fl(net3(x3), t3)
+        loss.backward()
+        opt3.step()
+
+    ms = gpu_ms(step3_focal, reps=3, warm=1)
+    emit(row="8f-4 HDenseFormer_2D_32 train step, PI-CAI shape, focal loss",
+         config="batch 24 of 2x384^2, fwd + DeepSuper FocalLoss('sum') + bwd + Adam, bf16", gpu_ms=ms,
+         samples_per_s=24 / ms * 1e3)
 except Exception as exc:  # report, do not hide: the row then says why it is missing
     emit(row="8f-4 PI-CAI shape", error=repr(exc)[:300])
