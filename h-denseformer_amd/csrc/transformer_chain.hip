@@ -110,7 +110,7 @@ __device__ __forceinline__ TfOutP chain_out(const ChainW& cw, float* base, int b
 // float4 <- W[g OQ + s0 + 4 j + e][n0 + i].
 __global__ __launch_bounds__(256) void tf_chain_pack_kernel(ChainW cw, const float* __restrict__ params, int64_t mstride,
                                                             int DM, int nl, float4* __restrict__ wpack) {
-  HDF_LIGHT_PRIO();   // (runs beside the first level-0 conv since round 5: plan.hip forward3d)
+  HDF_LIGHT_PRIO();   // (runs beside the first level-0 conv since round 5: exec.hip forward3d)
   const int m = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
   const int DMF = DM + 128, M = gridDim.y, nb = nl >> 2;
@@ -279,12 +279,12 @@ __device__ __forceinline__ void chain_arrive(unsigned* cnt, bool storing = true)
 // Giving up (round 6; rounds 5 trapped here, which killed the caller's HIP context): a sibling that has not arrived within
 // `c.ticks` of the 100 MHz real-time counter means the grid is not resident together -- the device is shared with something
 // that holds compute units.  The workgroup then leaves 1 + its id in the sync region's timeout word AND in the plan's
-// host-mapped flag word (system scope: the host reads it without synchronising, plan.hip chain_flag_check), stops waiting
+// host-mapped flag word (system scope: the host reads it without synchronising, exec.hip chain_flag_check), stops waiting
 // for the rest of the launch and runs to the end on whatever it reads; every other workgroup sees the word in its own poll
 // loop and does the same, so the launch ends within about one timeout.  Its results are garbage BY DEFINITION: dead
 // workgroups overwrite their rows of the branch output with NaN at the end of the kernel (which rows were lost: NaN does
 // not survive relu(InstanceNorm(.)) = fmaxf(.., 0) downstream), the plan's last launch of the call turns the head of every
-// output / of the gradient buffer into NaN when the timeout word is set (plan.hip: chain_poison_*_kernel), so the step's
+// output / of the gradient buffer into NaN when the timeout word is set (exec.hip: chain_poison_*_kernel), so the step's
 // loss and optimizer step are NaN rather than plausible, and the plan's next call returns HDF_ERR_CHAIN_TIMEOUT once and
 // routes this plan to the launch chain from then on.
 using ChainCtl = TfChainCtl;   // (transformer.h: host-mapped flag word + give-up deadline)
@@ -801,7 +801,7 @@ __global__ __launch_bounds__(CT) void tf_chain_fwd_kernel(ChainFwd a) {
     }
   }
   // a workgroup that gave up at a barrier overwrites its rows of the branch output with NaN (chain_wait; a marker of WHICH
-  // rows were lost -- what makes the step's loss NaN is plan.hip's chain_poison_outputs_kernel)
+  // rows were lost -- what makes the step's loss NaN is exec.hip's chain_poison_outputs_kernel)
   if (chain_any_dead(dead, reinterpret_cast<unsigned*>(s_red))) {
     const float qnan = __builtin_nanf("");
     for (int i = tid; i < nvalid * DM; i += CT) {
@@ -1711,7 +1711,7 @@ __global__ __launch_bounds__(CT) void tf_chain_bwd_kernel(ChainBwd a) {
     CHAIN_STAMPB(8);
   }
   // a workgroup that gave up at a barrier (chain_wait) overwrites its rows of block 0's input gradient with NaN: the patch
-  // embedding's gradients are then NaN (and plan.hip's chain_poison_grads_kernel marks the head of the gradient buffer)
+  // embedding's gradients are then NaN (and exec.hip's chain_poison_grads_kernel marks the head of the gradient buffer)
   if (chain_any_dead(dead, reinterpret_cast<unsigned*>(s_red))) {
     const float qnan = __builtin_nanf("");
     for (int i = tid; i < nvalid * DM; i += CT) {

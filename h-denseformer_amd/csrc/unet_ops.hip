@@ -415,7 +415,7 @@ __global__ __launch_bounds__(256) void upsample_fwd_kernel(const T* __restrict__
 // the block from the 3 x 3 x 3 low-resolution neighbourhood (the same separable x, y, z arithmetic as
 // upsample_fwd_kernel, plane by plane) and adds it in registers.  What it is for: at3's up-sampling (268 MB written at
 // 128^3, batch 2: 103 us) was the LAST launch of the transformer / UpConv chain the caller's stream waits for in the
-// forward (plan.hip: forward3d); with it here the wait ends at up3's InstanceNorm statistics, and this pass reads the
+// forward (exec.hip: forward3d); with it here the wait ends at up3's InstanceNorm statistics, and this pass reads the
 // 33 MB low-resolution tensor (L2-resident neighbours) instead of 268 MB.  The interpolated value is added in fp32
 // (the materialised at3 was rounded to the storage type first).
 // Registers: two interpolated planes (64 floats at 8 channels) + four norm vectors + the running maxima: one workgroup

@@ -3,7 +3,7 @@ factories and state_dict (Conv2d / ConvTranspose2d / InstanceNorm2d parameter sh
 [B, C, H, W] inputs, all arithmetic in libhdf_hip.so.
 
 Round 6: the library runs the 2-D model natively on depth-1 tensors (hdf_plan_create_2d: 2-D convolutions, transposed
-convolutions and weight gradients on the 9 centre-plane taps, MaxPool2d, bilinear x2; csrc/plan.hip "2-D embedding" for
+convolutions and weight gradients on the 9 centre-plane taps, MaxPool2d, bilinear x2; csrc/embed2d.hip "2-D embedding" for
 how the 2-D parameters sit in the 27-tap panels).  `net._embedded_2d = True` before the first forward selects the exact
 depth-16 replicated 3-D embedding of rounds 3-5 instead (16x ... 2x the arithmetic): the oracle of
 tests/test_gpu_model_2d.py."""

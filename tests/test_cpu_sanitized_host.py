@@ -1,6 +1,7 @@
-"""SURVEY 5.2 / VERDICT r03 #7c: the host side of csrc/plan.hip -- 1,900 lines of offset arithmetic: parameter table,
-workspace carving, named views, the 2-D embedding -- built with AddressSanitizer + UndefinedBehaviorSanitizer (CPU
-only: device code is not instrumented, GPU sanitizers are not available on this pool) and walked for the five BASELINE
+"""SURVEY 5.2 / VERDICT r03 #7c: csrc/plan.hip -- the plan and nothing else, ~500 lines of offset arithmetic: parameter
+table, layer table, workspace carving, named views, the 2-D embedding's job table -- built with AddressSanitizer +
+UndefinedBehaviorSanitizer (CPU only; the executor, the kernels and the operator entry points are the product's
+uninstrumented objects, GPU sanitizers are not available on this pool) and walked for the five BASELINE
 configs, three storage types and three batch sizes by tools/san_plan_walk.py in a child process that preloads the ASan
 runtime.  Any report (heap overflow in a table, signed overflow in an offset, misaligned access) fails the test."""
 import os

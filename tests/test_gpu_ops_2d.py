@@ -2,7 +2,7 @@
 (include/hdf.h: hdf_op_conv3d / hdf_op_conv3d_wgrad).  Reference: the torch 2-D ops models/HDenseFormer_2D.py composes
 (Conv2d k3 p1 :148-150, ConvTranspose2d k3 s2 p1 op1 :204-214 and their autograd), on storage-rounded operands.
 The packed weight panel keeps the 27-tap layout with the 2-D kernel on the centre depth plane (taps 9..17), which is what
-the plan's parameter embedding produces (csrc/plan.hip "2-D embedding")."""
+the plan's parameter embedding produces (csrc/embed2d.hip "2-D embedding")."""
 import pytest
 import torch
 import torch.nn.functional as F

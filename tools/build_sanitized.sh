@@ -1,8 +1,8 @@
 #!/bin/bash
-# CPU-only AddressSanitizer + UBSan build of the HOST side of csrc/plan.hip (layout, parameter table, 2-D embedding
-# offsets; device code is not instrumented: GPU sanitizers are not available on this pool).  The other objects are the
-# product's.  Output: h-denseformer_amd/lib/libhdf_hip_san.so; run it with the sanitizer runtimes preloaded
-# (tests/test_cpu_sanitized_host.py, tools/san_plan_walk.py).
+# CPU-only AddressSanitizer + UBSan build of csrc/plan.hip: the plan and nothing else (parameter table, layer table, 2-D
+# embedding jobs, workspace layout, the hdf_plan_* queries; the unit holds no device code).  The other objects -- executor,
+# kernels, operator entry points -- are the product's, uninstrumented.  Output: h-denseformer_amd/lib/libhdf_hip_san.so;
+# run it with the sanitizer runtimes preloaded (tests/test_cpu_sanitized_host.py, tools/san_plan_walk.py).
 set -e
 cd "$(dirname "$0")/../h-denseformer_amd"
 python build.py > /dev/null
