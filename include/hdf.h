@@ -263,7 +263,10 @@ int hdf_op_to_channels_last(int dtype, const float* x_ncdhw, void* out, int N, i
 int hdf_op_pack_weights(int dtype, const float* src, void* dst, int O, int I, int OP, int IP, int64_t so, int64_t si,
                         int flip, hdf_stream stream);
 /* mode 0: Conv3d(k3,s1,p1); mode 1: Conv3d(k3,s2,p1); mode 2: ConvTranspose3d(k3,s2,p1,op1).
- * in_scale/in_shift ([N][Cin], may be null): input is relu?(x*scale+shift).  stat_partials may be null. */
+ * in_scale/in_shift ([N][Cin], may be null): input is relu?(x*scale+shift).  stat_partials may be null.
+ * stat_partials (here, in hdf_op_conv3d_wr, hdf_op_conv3d_first and hdf_op_conv3d_split): every kernel sums the fp32
+ * value conv + bias BEFORE it is rounded to the storage type, not the stored value (and in an accumulating launch the
+ * kernels differ in whether the old output is included: do not combine accumulate with stat_partials). */
 int hdf_op_conv3d(int dtype, int mode, const void* in, int64_t in_pitch, int Cin, int N, int Di, int Hi, int Wi,
                   const void* w_packed, const float* bias, const float* in_scale, const float* in_shift, int in_relu,
                   void* out, int64_t out_pitch, int Cout, float* stat_partials, int accumulate, hdf_stream stream);

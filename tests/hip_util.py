@@ -73,3 +73,83 @@ def rel_err(a, b):
 def rel_l2(a, b):
     a, b = a.double(), b.double()
     return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+# ------------------------------------------------------------------------------------------------ rounding-aware checks
+# A kernel that takes 16-bit operands, accumulates in fp32 and stores ONE rounding of the result may differ from the fp64
+# value of the same expression by half a unit in the last place of the storage type plus the error of the fp32 accumulation
+# -- nothing else.  These checks hold every element to that; rel_err (max error / max reference) does not see a truncating
+# store, nor one voxel left out of a weight gradient.
+SIG_BITS = {F32: 24, BF16: 8, F16: 11}        # significand bits, the implicit one included
+MIN_EXP = {F32: -126, BF16: -126, F16: -14}   # exponent of the smallest normal; below it the spacing stays constant
+
+
+def ulp_of(ref64, dtype):
+    """spacing of the storage type at |ref64| (fp64 tensor): 2^(floor(log2|r|) - (bits - 1)), the subnormal spacing
+    (2^-24 for float16) below the smallest normal and at zero"""
+    _, e = torch.frexp(ref64.double().abs())                 # |r| = m * 2^e, m in [0.5, 1): floor(log2|r|) = e - 1
+    e = torch.where(ref64 == 0, torch.full_like(e, MIN_EXP[dtype]), e - 1).clamp_min(MIN_EXP[dtype])
+    return torch.exp2((e - (SIG_BITS[dtype] - 1)).double())
+
+
+def rounding_excess(got, ref64, dtype, acc):
+    """per element |got - ref64| / (0.5 ulp + acc): <= 1 where the element is one rounding of a value within acc of ref64"""
+    got, ref64 = got.double(), ref64.double()
+    assert got.shape == ref64.shape, (got.shape, ref64.shape)
+    return (got - ref64).abs() / (0.5 * ulp_of(ref64, dtype) + acc)
+
+
+def _worst(ratio, got, ref64, unit, unit_name, what):
+    bad = ratio > 1.0
+    flat = int(torch.where(torch.isnan(ratio), torch.full_like(ratio, float("inf")), ratio).argmax())
+    idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(flat), ratio.shape))
+    g, r = float(got.double().flatten()[flat]), float(ref64.double().flatten()[flat])
+    return ("%s: %d of %d elements outside the bound; worst at index %s: got %.9g, reference %.9g, error %.3f %s, "
+            "%.3f x the bound" % (what, int(bad.sum()) + int(torch.isnan(ratio).sum()), ratio.numel(), idx, g, r,
+                                  abs(g - r) / float(unit.flatten()[flat]), unit_name, float(ratio.flatten()[flat])))
+
+
+def check_rounded(got, ref64, dtype, acc, what="output"):
+    """assert, for EVERY element, |got - ref64| <= 0.5 * ulp_of(ref64, dtype) + acc.  got: the kernel's output (any float
+    tensor, converted exactly to fp64); ref64: the fp64 reference on the storage-rounded operands; acc: an absolute
+    allowance for the fp32 accumulation, taken from the reference alone.  Returns the worst error / bound (<= 1)."""
+    assert acc >= 0.0 and acc == acc
+    got, ref64 = got.double(), ref64.double()
+    ratio = rounding_excess(got, ref64, dtype, acc)
+    ok = bool((ratio <= 1.0).all())          # (a NaN compares false: a NaN output fails)
+    assert ok, _worst(ratio, got, ref64, ulp_of(ref64, dtype), "ulp", what)
+    return float(ratio.max())
+
+
+def check_fp32_sum(got, ref64, acc, what="output"):
+    """an fp32 result accumulated from exact products (the weight gradients): no storage rounding, so for EVERY element
+    |got - ref64| <= acc + 2^-24 |ref64|.  Returns the worst error / bound (<= 1)."""
+    assert acc >= 0.0 and acc == acc
+    got, ref64 = got.double(), ref64.double()
+    assert got.shape == ref64.shape, (got.shape, ref64.shape)
+    bound = acc + 2.0 ** -24 * ref64.abs()
+    ratio = (got - ref64).abs() / bound.clamp_min(1e-300)
+    ok = bool((ratio <= 1.0).all())
+    assert ok, _worst(ratio, got, ref64, bound.clamp_min(1e-300), "bounds", what)
+    return float(ratio.max())
+
+
+def signed_rounding_bias(got, ref64, dtype):
+    """(bias, n_used, n): the mean of (got - ref64) * sign(ref64) / ulp over the elements with |ref64| >= max|ref64| / 64
+    (below that the accumulation error is not small against the ulp).  Round-to-nearest-even gives 0 with standard
+    deviation 0.289 / sqrt(n_used); a truncating store gives -0.5."""
+    got, ref64 = got.double(), ref64.double()
+    use = ref64.abs() >= ref64.abs().max() / 64
+    e = ((got - ref64) * torch.sign(ref64) / ulp_of(ref64, dtype))[use]
+    return float(e.mean()), int(use.sum()), ref64.numel()
+
+
+def check_rounding_bias(got, ref64, dtype, what="output"):
+    """a 16-bit output must be rounded without bias: |bias| <= 6 sigma of round-to-nearest, on at least 90 % of the elements
+    and at least 10 000 of them (conditions on the test's own data)"""
+    assert dtype in (BF16, F16)
+    bias, used, n = signed_rounding_bias(got, ref64, dtype)
+    assert used >= 0.9 * n and used >= 10000, "%s: the bias statistic uses %d of %d elements" % (what, used, n)
+    assert abs(bias) <= 6 * 0.289 / used ** 0.5, "%s: signed rounding bias %.4f ulp over %d elements (bound %.4f)" % (
+        what, bias, used, 6 * 0.289 / used ** 0.5)
+    return bias
