@@ -1,5 +1,5 @@
 // Process state (last error, compute-unit budget) and the one-to-one C ABI wrappers of the operator launchers: losses,
-// metrics, normalisation, sliding window, Adam, hdf_op_*.  Nothing here touches a plan.
+// metrics, normalisation, sliding window, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
 #include <atomic>
 #include <algorithm>
 #include <cstdarg>
@@ -8,6 +8,7 @@
 #include "../../include/hdf.h"
 #include "conv_igemm.h"
 #include "loss.h"
+#include "optim.h"
 #include "transformer.h"
 #include "unet_ops.h"
 
@@ -174,6 +175,13 @@ int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
   HDF_CHECK_ARG(step >= 1, "adam: step=%d must start at 1", step);
   return hdf_launch_adam(params, grads, exp_avg, exp_avg_sq, decay_mask, n, lr, beta1, beta2, eps, weight_decay, step,
                          grad_scale, (hipStream_t)stream);
+}
+int hdf_optim_step(int rule, float* params, const float* grads, float* state1, float* state2, const uint8_t* decay_mask,
+                   int64_t n, float lr_decay, float lr_rest, float wd_decay, float wd_rest, float beta1, float beta2,
+                   float eps, int nesterov, float grad_mul, const float* grad_scale, const float* found_inf,
+                   int32_t* step_state, hdf_stream stream) {
+  return hdf_launch_optim(rule, params, grads, state1, state2, decay_mask, n, lr_decay, lr_rest, wd_decay, wd_rest, beta1,
+                          beta2, eps, nesterov, grad_mul, grad_scale, found_inf, step_state, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------- operator level

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "loss.h"
+#include "optim.h"
 
 namespace {
 constexpr int MAXC = 8;
@@ -595,14 +596,11 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
                             float* __restrict__ v, const uint8_t* __restrict__ decay, int64_t n, float lr, float b1,
                             float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float pi = p[i];
-    float gi = g[i] * gscale + ((decay && decay[i]) ? wd * pi : 0.f);
-    float mi = b1 * m[i] + (1.f - b1) * gi;
-    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_elem(pi, g[i], mi, vi, decay && decay[i], gscale, lr, b1, b2, eps, wd, bc1, bc2_sqrt);   // optim.h
     m[i] = mi;
     v[i] = vi;
-    float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = pi - (lr / bc1) * (mi / denom);
+    p[i] = pi;
   }
 }
 }  // namespace

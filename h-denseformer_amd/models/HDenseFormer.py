@@ -256,11 +256,12 @@ class HDenseFormer(nn.Module):
         """uint8 mask over the flat buffer: 1 where trainer.py:812-817 applies weight decay
         (ndim > 1 and name not ending in '.bias')."""
         flat = self.flat_parameters()
-        mask = torch.zeros(flat.numel(), dtype=torch.uint8)
+        # filled where it lives (a host copy sent over would synchronise the first optimizer step with the device)
+        mask = torch.zeros(flat.numel(), dtype=torch.uint8, device=flat.device)
         for name, off, numel, shape in self._plan(_lib.F32).table:
             if not (len(shape) == 1 or name.endswith(".bias")):
                 mask[off: off + numel] = 1
-        return mask.to(flat.device)
+        return mask
 
     # ------------------------------------------------------------------------------ execution
     def _pick_dtype(self, x):

@@ -255,6 +255,30 @@ int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   float grad_scale, hdf_stream stream);
 
+/* ---- flat optimizer step: the three optimizers of trainer.py:793-840 as torch computes them in fp32, one streaming
+ * kernel over the flat buffers (plus a one-thread prologue), nothing read back by the host.
+ * rule: HDF_OPTIM_ADAM (L2 decay added to the gradient: the rule of hdf_adam_step, same bits), HDF_OPTIM_ADAMW
+ * (decoupled: p *= 1 - lr*wd before the moment update), HDF_OPTIM_SGD (L2 decay, momentum buffer with dampening 0,
+ * initialised to the gradient by the first step; nesterov != 0: g + momentum*buf).
+ * state1 / state2: exp_avg / exp_avg_sq, or the momentum buffer / null for SGD; beta1 is the momentum of SGD (beta2 and
+ * eps unused).  Two parameter groups chosen by the decay_mask byte: lr_decay / wd_decay where it is set, lr_rest /
+ * wd_rest elsewhere.  The gradient used is g * grad_mul / *grad_scale.
+ * grad_scale, found_inf (each may be null): DEVICE pointers to one fp32, the protocol of torch.amp.GradScaler for
+ * optimizers that unscale inside their step.  *found_inf != 0: the call leaves parameters, state buffers and the step
+ * counter bit for bit untouched.
+ * step_state: HDF_OPTIM_STATE_WORDS int32 on the device, zeroed by the caller before the first step and then left alone.
+ * Word 0 is the number of steps taken (the bias correction's exponent; saved and restored with the state buffers); the
+ * other words are scratch of the call.
+ * params, grads, state1, state2 16-byte aligned, decay_mask 4-byte aligned; any n >= 0. */
+#define HDF_OPTIM_ADAM 0
+#define HDF_OPTIM_ADAMW 1
+#define HDF_OPTIM_SGD 2
+#define HDF_OPTIM_STATE_WORDS 8
+int hdf_optim_step(int rule, float* params, const float* grads, float* state1, float* state2, const uint8_t* decay_mask,
+                   int64_t n, float lr_decay, float lr_rest, float wd_decay, float wd_rest, float beta1, float beta2,
+                   float eps, int nesterov, float grad_mul, const float* grad_scale, const float* found_inf,
+                   int32_t* step_state, hdf_stream stream);
+
 /* ---- operator level (what nn.Conv3d / ConvTranspose3d / InstanceNorm3d / MaxPool3d / F.interpolate bind
  *      in the reference, HDenseFormer.py:148-175,199-227).  Channels-last activations with a voxel pitch. -- */
 int hdf_op_to_channels_last(int dtype, const float* x_ncdhw, void* out, int N, int C, int CP, int64_t voxels,
