@@ -1,4 +1,10 @@
-// Argument blocks of the implicit-GEMM 3x3x3 convolution family (see conv_igemm.hip).
+// Argument blocks and host entry points of the implicit-GEMM 3x3x3 convolution family.  One group of declarations per unit:
+//   conv_igemm.hip  hdf_launch_conv (routing), weight layout, statistics geometry
+//   conv_s2.hip     the specialised stride-2 kernels hdf_launch_conv routes to
+//   conv_wr.hip     weights-in-registers form of the stride-1 launches
+//   conv_first.hip  the encoder's first layer and its weight gradient
+//   conv_wgrad.hip  weight gradients
+//   conv_pack.hip   weight packers
 #pragma once
 #include "hdf_common.h"
 
@@ -78,17 +84,42 @@ struct WgradArgs {
   int64_t ap_out_pitch = 0;
   const float* ap_tab[7] = {};  // scale, shift, mean, rstd, k1, ka, kb: [N][SC] each
 };
-bool hdf_wgrad_apply_takes(int dtype, int stride, const WgradArgs& a);
 
-// conv_wr.hip: weights-in-registers form of the mode-0 launches with 64- / 128-byte rows at >= 48^3 (16-bit storage)
-// csrc/conv_first.hip: the encoder's first layer (1..4 real input channels, 16-bit storage) with tap-packed K.  Reads the
+// ---- conv_igemm.hip
+int hdf_launch_conv(int dtype, int mode /*0 conv s1, 1 conv s2, 2 convT*/, const ConvArgs& a, hipStream_t st);
+// tiles per sample of the stat partials; row_bytes = Cin*sizeof(storage) selects the kernel variant (pass a
+// large value for the upper bound used to size buffers)
+int hdf_conv_stat_tiles(int mode, int Do, int Ho, int Wo, int row_bytes);
+// can this mode-0 launch take the bs_* fields (else the caller runs hdf_launch_in_bwd_reduce)?
+bool hdf_conv_bwd_stats_ok(int dtype, const ConvArgs& a);
+// Weight layout the conv launch of this shape reads.  0: [27][CoutP][Cin] rows.  1: fragment-major, for the launches
+// that take conv_igemm_kernel's pipelined path (weight fragments straight from L2): per tap, per 32-channel output
+// block, per 32-byte step of the input-channel row, the 32 rows x 32 bytes one wave loads form ONE contiguous 1 KB
+// block -- a fragment load touches 8 full cache lines instead of 32 lines of which it uses 32 bytes each.
+int hdf_conv_weight_layout(int dtype, int mode, int Cin, int Do, int Ho, int Wo);
+
+// ---- conv_s2.hip: *_takes = the launch is one of this kernel's (hdf_launch_conv asks in this order per mode)
+bool hdf_conv_gather_s2_takes(int dtype, const ConvArgs& a);   // mode 1
+int hdf_launch_conv_gather_s2(int dtype, const ConvArgs& a, hipStream_t st);
+bool hdf_convt_ws_takes(int dtype, const ConvArgs& a);         // mode 2
+int hdf_launch_convt_ws(int dtype, const ConvArgs& a, hipStream_t st);
+bool hdf_convt_fused_rows(int row_bytes);                      // row widths convt_fused_kernel is instantiated for
+bool hdf_convt_fused_takes(int dtype, const ConvArgs& a);      // mode 2, 3-D and depth-1 (2-D) tensors
+int hdf_launch_convt_fused(int dtype, const ConvArgs& a, hipStream_t st);
+
+// ---- conv_wr.hip: weights-in-registers form of the mode-0 launches with 64- / 128-byte rows at >= 48^3 (16-bit storage)
+bool hdf_conv_wr_can(int dtype, const ConvArgs& a);    // the kernel handles this launch
+bool hdf_conv_wr_takes(int dtype, const ConvArgs& a);  // ... and the plan routes it there
+int hdf_launch_conv_wr(int dtype, const ConvArgs& a, hipStream_t st);
+
+// ---- conv_first.hip: the encoder's first layer (1..4 real input channels, 16-bit storage) with tap-packed K.  Reads the
 // fp32 torch-layout weights itself; stat_partials as hdf_launch_conv with WS_STAT_ROWS rows per sample.
 bool hdf_conv_first_can(int dtype, int Cin, int Cout, int D, int H, int W, int64_t in_pitch);
 bool hdf_conv_first_takes(int dtype, int Cin, int Cout, int D, int H, int W, int64_t in_pitch);
 int hdf_launch_conv_first(int dtype, const void* in, int64_t in_pitch, int Cin, int N, int D, int H, int W,
                           const float* w32, const float* bias, void* out, int64_t out_pitch, int Cout,
                           float* stat_partials, hipStream_t st);
-// the same layer's weight gradient (csrc/conv_first.hip): dw in the torch layout [Cout][Cin][27], fp32
+// the same layer's weight gradient: dw in the torch layout [Cout][Cin][27], fp32
 bool hdf_wgrad_first_takes(int dtype, int Cin, int Cout, int D, int H, int W, int64_t x_pitch, int64_t dy_pitch);
 // in_bwd (optional): `dy` is the gradient w.r.t. the layer's activation relu(IN(y)); the kernel applies the second pass of that
 // InstanceNorm(+ReLU)'s backward (hdf_launch_in_bwd_apply's arithmetic and storage rounding) while it stages the rows, so
@@ -101,18 +132,14 @@ struct WgradFirstIn {
 int hdf_launch_wgrad_first(int dtype, const void* dy, int64_t dy_pitch, int Cout, const void* x, int64_t x_pitch, int Cin,
                            int N, int D, int H, int W, float* dw, int accumulate, void* workspace, size_t workspace_bytes,
                            hipStream_t st, const WgradFirstIn* in_bwd = nullptr);
-bool hdf_conv_wr_can(int dtype, const ConvArgs& a);    // the kernel handles this launch
-bool hdf_conv_wr_takes(int dtype, const ConvArgs& a);  // ... and the plan routes it there
-int hdf_launch_conv_wr(int dtype, const ConvArgs& a, hipStream_t st);
-int hdf_launch_conv(int dtype, int mode /*0 conv s1, 1 conv s2, 2 convT*/, const ConvArgs& a, hipStream_t st);
-// tiles per sample of the stat partials; row_bytes = Cin*sizeof(storage) selects the kernel variant (pass a
-// large value for the upper bound used to size buffers)
-int hdf_conv_stat_tiles(int mode, int Do, int Ho, int Wo, int row_bytes);
-// can this mode-0 launch take the bs_* fields (else the caller runs hdf_launch_in_bwd_reduce)?
-bool hdf_conv_bwd_stats_ok(int dtype, const ConvArgs& a);
+
+// ---- conv_wgrad.hip
+bool hdf_wgrad_apply_takes(int dtype, int stride, const WgradArgs& a);
 int hdf_launch_wgrad(int dtype, int stride, WgradArgs a, float* dw, int sc_store, int lc_store, int accumulate,
                      void* workspace, size_t workspace_bytes, hipStream_t st);
 size_t hdf_wgrad_workspace_bytes(int stride, int N, int Ds, int Hs, int Ws, int SC, int LC);
+
+// ---- conv_pack.hip
 // every weight pack of a training step in ONE launch (42 separate 6-us launches otherwise)
 struct PackJob {
   int64_t src_off;  // floats from the parameter base
@@ -120,11 +147,6 @@ struct PackJob {
   int O, I, OP, IP, so, si, flip;
   int frag;  // 1: fragment-major destination (hdf_conv_weight_layout)
 };
-// Weight layout the conv launch of this shape reads.  0: [27][CoutP][Cin] rows.  1: fragment-major, for the launches
-// that take conv_igemm_kernel's pipelined path (weight fragments straight from L2): per tap, per 32-channel output
-// block, per 32-byte step of the input-channel row, the 32 rows x 32 bytes one wave loads form ONE contiguous 1 KB
-// block -- a fragment load touches 8 full cache lines instead of 32 lines of which it uses 32 bytes each.
-int hdf_conv_weight_layout(int dtype, int mode, int Cin, int Do, int Ho, int Wo);
 constexpr int HDF_MAX_PACK_JOBS = 64;
 int hdf_launch_pack_batch(int dtype, const float* params, char* ws, const PackJob* jobs, int njobs, hipStream_t st);
 int hdf_launch_pack_w(int dtype, const float* src, void* dst, int O, int I, int OP, int IP, int64_t so, int64_t si,

@@ -1,6 +1,8 @@
-// Pieces shared by the convolution kernels of conv_igemm.hip and conv_wr.hip: the MFMA wrapper per storage type, the
-// MFMA-row -> tile-voxel map of the 4x8x8 tile family, the LDS-only workgroup barrier and the persistent kernels' tile
-// record.
+// Pieces shared by the convolution kernels: the MFMA wrapper per storage type, the generic halo-box staging (PITCH,
+// stage_box), the MFMA-row -> tile-voxel map of the 4x8x8 tile family, the LDS-only workgroup barrier, the persistent
+// kernels' tile record, the zero line of the LDS-DMA kernels and the phase stamps of a -DWS_DBG_STAMPS build.
+// Users: conv_igemm.hip, conv_wgrad.hip and conv_s2.hip (any of it), conv_wr.hip and conv_first.hip (Mma, the row maps,
+// WS_BARRIER, WsTile).
 #pragma once
 #include "hdf_common.h"
 
@@ -29,6 +31,72 @@ struct Mma<float> {
       c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a[s]), __uint_as_float(b[s]), c, 0, 0, 0);
   }
 };
+
+constexpr int PITCH = 80;  // LDS bytes per voxel row: 64 payload + 16 pad
+
+// Stage a box of voxels (channels [c0, c0 + chunk_elems)) of a pitched NDHWC tensor into LDS with the
+// optional per-(n,channel) affine(+relu) transform.  Voxels outside the tensor and channels >= C
+// become zeros (zero padding applies to the TRANSFORMED activation).
+template <typename T, int BD, int BH, int BW, int ROWB /*payload bytes per row*/, int LPITCH>
+__device__ __forceinline__ void stage_box(char* lds, const T* __restrict__ src, int64_t pitch, int C, int n, int D,
+                                          int H, int W, int oz, int oy, int ox, int c0, int row_bytes,
+                                          const float* __restrict__ scale, const float* __restrict__ shift, int relu) {
+  constexpr int EPC = ST<T>::EPC;
+  const int cpv = row_bytes >> 4;  // 16-B chunks per voxel row (power of two)
+  const int cpv_shift = (cpv == 32) ? 5 : (cpv == 16) ? 4 : (cpv == 8) ? 3 : (cpv == 4) ? 2 : (cpv == 2) ? 1 : 0;
+  const int total = (BD * BH * BW) << cpv_shift;
+  const int part = threadIdx.x & (cpv - 1);  // constant per thread (256 % cpv == 0)
+  const int cbase = c0 + part * EPC;
+  float sc[EPC], sh[EPC];
+  const bool xf = (scale != nullptr);
+  if (xf) {
+#pragma unroll
+    for (int e = 0; e < EPC; e++) {
+      bool ok = (cbase + e) < C;
+      sc[e] = ok ? scale[(int64_t)n * C + cbase + e] : 0.f;
+      sh[e] = ok ? shift[(int64_t)n * C + cbase + e] : 0.f;
+    }
+  }
+  const bool chan_ok = cbase < C;  // C is a multiple of EPC
+  // Batches of U chunks per thread: all U loads are issued back to back (UNCONDITIONAL, from a clamped address:
+  // a per-element `if (ok) v = load` makes hipcc branch around every load and wait for each one in turn --
+  // cdna_hip_programming.md, projection-GEMM trap (c)), then transformed and written to LDS.
+  constexpr int U = 5;
+  for (int id0 = threadIdx.x; id0 < total; id0 += 256 * U) {
+    u32x4 v[U];
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      int id = min(id0 + 256 * u, total - 1);
+      int vox = id >> cpv_shift;
+      int bz = vox / (BH * BW);
+      int rem = vox - bz * (BH * BW);
+      int by = rem / BW;
+      int bx = rem - by * BW;
+      int iz = oz + bz, iy = oy + by, ix = ox + bx;
+      ok[u] = chan_ok && (unsigned)iz < (unsigned)D && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
+      const T* p = ok[u] ? src + ((((int64_t)n * D + iz) * H + iy) * W + ix) * pitch + cbase : src;
+      v[u] = *reinterpret_cast<const u32x4*>(p);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      int id = id0 + 256 * u;
+      u32x4 w = v[u];
+      if (xf) {
+        float f[EPC];
+        ST<T>::unpack(w, f);
+#pragma unroll
+        for (int e = 0; e < EPC; e++) {
+          f[e] = f[e] * sc[e] + sh[e];
+          if (relu) f[e] = fmaxf(f[e], 0.f);
+        }
+        w = ST<T>::pack(f);
+      }
+      if (!ok[u]) w = u32x4{0u, 0u, 0u, 0u};
+      if (id < total) *reinterpret_cast<u32x4*>(lds + (id >> cpv_shift) * LPITCH + part * 16) = w;
+    }
+  }
+}
 
 // MFMA row (0..31) -> (dz in 0..3, x in 0..7).  ds_read_b128 services lanes {0-3,12-15,20-27} and {4-11,16-19,
 // 28-31} (and the same +32) as groups; group 1 gets z in {0,2}, group 2 z in {1,3}: box row = 100*z + 10*y + x
@@ -60,5 +128,23 @@ struct WsTile {
   int k;  // index in the list the tile came from (border pass)
 };
 
+// 16 zero bytes: the source of LDS-DMA slots that lie outside the tensor (zero padding)
+__device__ __attribute__((aligned(16))) uint32_t g_zero_line[4] = {0u, 0u, 0u, 0u};
 
 }  // namespace
+
+// -DWS_DBG_STAMPS: shader-clock stamps per phase of a persistent kernel (conv_ws2_kernel, conv_wgrad2_kernel).  The kernel
+// declares `unsigned long long tacc[8]` and `tlast`; WS2_STAMP(k) adds the cycles since the previous stamp to tacc[k].
+#ifdef WS_DBG_STAMPS
+#define WS2_STAMP(k)                                       \
+  {                                                        \
+    __builtin_amdgcn_sched_barrier(0);                     \
+    unsigned long long t_ = __builtin_amdgcn_s_memtime();  \
+    __builtin_amdgcn_s_waitcnt(0xC07F);                    \
+    __builtin_amdgcn_sched_barrier(0);                     \
+    tacc[k] += t_ - tlast;                                 \
+    tlast = t_;                                            \
+  }
+#else
+#define WS2_STAMP(k)
+#endif

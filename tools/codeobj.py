@@ -3,7 +3,8 @@
 libhdf_hip.so carries one clang offload bundle per translation unit in .hip_fatbin; each holds a gfx950 ELF whose
 NT_AMDGPU_METADATA note lists, per kernel: registers, spills, scratch (private segment) and static LDS.
 `kernels(so)` returns {demangled name: record}; `disassemble(so, name_substring)` the instruction mnemonics of one kernel.
-CLI: python tools/codeobj.py [regex]  -> one line per kernel."""
+CLI: python tools/codeobj.py [regex]        -> one line per kernel
+     python tools/codeobj.py --diff A.so B.so -> what a refactor changed between two builds (exit status 1 if anything)."""
 import os
 import re
 import struct
@@ -69,21 +70,99 @@ def kernels(so=LIB):
     return recs
 
 
+def _objdump(img, symbol=None):
+    """llvm-objdump -d of one code object (of one symbol): [(symbol, instruction line)].  A failed whole-object run raises;
+    with a symbol, a code object that lacks it just yields nothing"""
+    with tempfile.NamedTemporaryFile(suffix=".elf") as f:
+        f.write(img)
+        f.flush()
+        sel = [f"--disassemble-symbols={symbol}"] if symbol else []
+        r = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn"] + sel + [f.name],
+                           capture_output=True, text=True)
+    if r.returncode != 0 and not symbol:
+        raise RuntimeError("llvm-objdump failed:\n" + r.stderr[-2000:])
+    out, cur = [], None
+    for line in r.stdout.splitlines():
+        m = re.match(r"[0-9a-f]+ <(\S+)>:", line)
+        if m:
+            cur = m.group(1)
+        elif re.match(r"\s+[a-z_0-9]+ ", line) or re.match(r"\s+[sv]_[a-z_0-9]+", line):
+            out.append((cur, line.strip()))
+    return out
+
+
 def disassemble(mangled, so=LIB):
     """instruction lines of one kernel (by mangled name)"""
     for img in code_objects(so):
-        with tempfile.NamedTemporaryFile(suffix=".elf") as f:
-            f.write(img)
-            f.flush()
-            r = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", f"--disassemble-symbols={mangled}",
-                                f.name], capture_output=True, text=True)
-        lines = [l.strip() for l in r.stdout.splitlines() if re.match(r"\s+[a-z_0-9]+ ", l) or re.match(r"\s+[sv]_[a-z_0-9]+", l)]
+        lines = [l for _, l in _objdump(img, mangled)]
         if lines:
             return lines
     return []
 
 
+RESOURCES = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
+             "group_segment_fixed_size", "max_flat_workgroup_size")
+
+
+def instruction_streams(so=LIB):
+    """{mangled name: instruction lines} of every kernel, one objdump run per code object; made comparable between builds:
+    the trailing comment (address, encoding, branch-target label) is dropped -- the relative branch offset stays -- as is
+    the padding behind the last s_endpgm, and the literal of an s_add_u32 / s_addc_u32 that follows s_getpc_b64 (the
+    pc-relative address of a global, which moves with the layout of the code object)"""
+    out = {}
+    for img in code_objects(so):
+        pcrel = 0
+        for sym, line in _objdump(img):
+            cur = out.setdefault(sym, [])
+            ins = re.sub(r"\s+", " ", line.split("//")[0].strip())
+            if not cur:
+                pcrel = 0
+            if ins.startswith("s_getpc_b64"):
+                pcrel = 3
+            elif pcrel and re.match(r"s_addc?_u32 ", ins):
+                ins = re.sub(r", (0x[0-9a-f]+|\d+)$", ", <pcrel>", ins)
+            pcrel = max(0, pcrel - 1)
+            cur.append(ins)
+    for name, lines in out.items():
+        while lines and re.match(r"s_nop|s_code_end", lines[-1]):
+            lines.pop()
+    return out
+
+
+def diff(so_a, so_b):
+    """print the differences between two builds; returns their number"""
+    ka = {k["mangled"]: k for k in kernels(so_a).values()}
+    kb = {k["mangled"]: k for k in kernels(so_b).values()}
+    n = 0
+    for tag, only in (("only in A", sorted(set(ka) - set(kb))), ("only in B", sorted(set(kb) - set(ka)))):
+        for m in only:
+            print("%s: %s" % (tag, (ka.get(m) or kb[m])["name"]))
+            n += 1
+    common = sorted(set(ka) & set(kb))
+    sa, sb = instruction_streams(so_a), instruction_streams(so_b)
+    for tag, streams in (("A", sa), ("B", sb)):
+        missing = [m for m in common if not streams.get(m)]
+        if missing:
+            raise RuntimeError("no instruction stream in %s for %d kernels, e.g. %s" % (tag, len(missing), missing[0]))
+    for m in common:
+        ra, rb = [ka[m].get(r, 0) for r in RESOURCES], [kb[m].get(r, 0) for r in RESOURCES]
+        if ra != rb:
+            print("resources differ: %s\n    %s" % (ka[m]["name"], ", ".join(
+                "%s %d -> %d" % (r, x, y) for r, x, y in zip(RESOURCES, ra, rb) if x != y)))
+            n += 1
+        if sa[m] != sb[m]:
+            la, lb = sa[m], sb[m]
+            first = next((i for i, (x, y) in enumerate(zip(la, lb)) if x != y), min(len(la), len(lb)))
+            print("instructions differ: %s\n    %d -> %d instructions, first difference at %d: %s | %s" % (
+                ka[m]["name"], len(la), len(lb), first, la[first] if first < len(la) else "-", lb[first] if first < len(lb) else "-"))
+            n += 1
+    print("%d kernels in A, %d in B, %d common, %d differences" % (len(ka), len(kb), len(common), n))
+    return n
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--diff":
+        sys.exit(1 if diff(sys.argv[2], sys.argv[3]) else 0)
     pat = sys.argv[1] if len(sys.argv) > 1 else ""
     for n, k in sorted(kernels().items()):
         if pat and not re.search(pat, n):

@@ -9,8 +9,9 @@ for v in $VARS; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form -mllvm -pragma-unroll-threshold=1000000 -DWR_DBG_$v -c csrc/conv_wr.hip -o build/wr_$v/conv_wr.o &
 done
 wait
+# every product object except conv_wr.o (the list follows build.py's SOURCES: a source added there is linked here too)
+objs=$(python -c "import build; print(' '.join('build/' + s[:-4] + '.o' for s in build.SOURCES if s != 'conv_wr.hip'))")
 for v in $VARS; do
-  objs="build/conv_igemm.o build/conv_first.o build/unet_ops.o build/transformer.o build/transformer_fused.o build/transformer_chain.o build/loss.o build/plan.o"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o lib/libhdf_hip_wr_$v.so $objs build/wr_$v/conv_wr.o
 done
 ls -la lib/
