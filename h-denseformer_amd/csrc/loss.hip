@@ -757,7 +757,8 @@ int hdf_launch_loss_focal_bwd(int dtype, const void* const* logits, const float*
 
 int hdf_launch_dice_counts(int dtype, const void* logits, const float* target, int N, int C, int64_t V,
                            unsigned long long* counts, hipStream_t st) {
-  HDF_CHECK_ARG(C <= MAXC, "dice: n_cls=%d", C);
+  HDF_CHECK_ARG(C >= 1 && C <= MAXC && V >= 1 && N >= 1, "dice: n_cls=%d (1..%d) voxels=%lld batch=%d", C, MAXC, (long long)V,
+                N);
   hipError_t e = hipMemsetAsync(counts, 0, (size_t)N * MAXC * 3 * sizeof(unsigned long long), st);
   if (e != hipSuccess) {
     hdf_set_error("dice: memset failed: %s", hipGetErrorString(e));
@@ -772,7 +773,8 @@ int hdf_launch_dice_counts(int dtype, const void* logits, const float* target, i
 
 int hdf_launch_confusion(int dtype, const void* logits, const float* target, int N, int C, int64_t V,
                          unsigned long long* conf, int accumulate, hipStream_t st) {
-  HDF_CHECK_ARG(C <= MAXC, "confusion: n_cls=%d", C);
+  HDF_CHECK_ARG(C >= 1 && C <= MAXC && V >= 1 && N >= 1, "confusion: n_cls=%d (1..%d) voxels=%lld batch=%d", C, MAXC,
+                (long long)V, N);
   if (!accumulate) {
     hipError_t e = hipMemsetAsync(conf, 0, (size_t)MAXC * MAXC * sizeof(unsigned long long), st);
     if (e != hipSuccess) {

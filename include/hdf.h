@@ -208,7 +208,8 @@ int hdf_loss_focal_backward(int dtype, const void* out0, const void* out1, const
                             float dice_weight, const float* class_weight, int dice_ignore_index, const void* workspace,
                             const float* grad_out, void* dout0, void* dout1, void* dout2, void* dout3,
                             hdf_stream stream);
-/* hard-argmax Dice counts of trainer.py:919-945: counts[batch][8][3] = (|P&T|, |P|, |T|) per class, uint64 */
+/* hard-argmax Dice counts of trainer.py:919-945: counts[batch][8][3] = (|P&T|, |P|, |T|) per class, uint64.
+ * This and hdf_confusion_matrix refuse (HDF_ERR_ARG) batch < 1, voxels < 1 and n_cls outside 1..8. */
 int hdf_dice_counts(int dtype, const void* logits, const float* target_onehot, int batch, int n_cls, int64_t voxels,
                     uint64_t* counts, hdf_stream stream);
 

@@ -144,12 +144,20 @@ def signed_rounding_bias(got, ref64, dtype):
     return float(e.mean()), int(use.sum()), ref64.numel()
 
 
-def check_rounding_bias(got, ref64, dtype, what="output"):
-    """a 16-bit output must be rounded without bias: |bias| <= 6 sigma of round-to-nearest, on at least 90 % of the elements
-    and at least 10 000 of them (conditions on the test's own data)"""
+def check_rounding_bias(got, ref64, dtype, what="output", expected=0.0):
+    """a 16-bit output must be rounded without bias: |bias - expected| <= 6 sigma of round-to-nearest, on at least 90 % of
+    the elements and at least 10 000 of them (conditions on the test's own data).  expected: the bias that rounding ref64
+    itself to nearest-even has on this data (rne_bias), 0 where the fractions of an ulp that the rounding drops are
+    uniformly distributed -- outputs of a long accumulation; not a softmax gradient of 16-bit logits, whose values cluster"""
     assert dtype in (BF16, F16)
     bias, used, n = signed_rounding_bias(got, ref64, dtype)
     assert used >= 0.9 * n and used >= 10000, "%s: the bias statistic uses %d of %d elements" % (what, used, n)
-    assert abs(bias) <= 6 * 0.289 / used ** 0.5, "%s: signed rounding bias %.4f ulp over %d elements (bound %.4f)" % (
-        what, bias, used, 6 * 0.289 / used ** 0.5)
+    assert abs(bias - expected) <= 6 * 0.289 / used ** 0.5, (
+        "%s: signed rounding bias %.4f ulp over %d elements (round-to-nearest of the reference: %.4f, bound %.4f)" % (
+            what, bias, used, expected, 6 * 0.289 / used ** 0.5))
     return bias
+
+
+def rne_bias(ref64, dtype):
+    """the signed rounding bias of ref64 rounded once, to nearest-even, into the storage type: a property of the data"""
+    return signed_rounding_bias(ref64.double().to(TDT[dtype]), ref64, dtype)[0]

@@ -69,6 +69,23 @@ def test_plan_rejects_bad_configs(lib):
         assert rc != 0 and len(lib.hdf_last_error()) > 0
 
 
+def test_metric_entries_refuse_empty_and_out_of_range_arguments(lib):
+    """hdf_dice_counts / hdf_confusion_matrix with no voxels (a zero-block grid), no samples or a class count outside
+    1..8 (0 and negatives passed `n_cls <= 8`): HDF_ERR_ARG (1) with a message, before the memset and the launch (on this
+    host, which has no device, either would come back as HDF_ERR_HIP = 2).  The addresses are never dereferenced."""
+    from hdf_rt import _lib
+    buf = (C.c_float * 64)()
+    a = C.addressof(buf)
+    for what, (n, c, v) in {"no voxels": (1, 3, 0), "negative voxels": (1, 3, -5), "no classes": (1, 0, 64),
+                            "negative classes": (1, -2, 64), "nine classes": (1, 9, 64), "no samples": (0, 3, 64)}.items():
+        for dtype in (_lib.F32, _lib.BF16, _lib.F16):
+            rc = lib.hdf_dice_counts(dtype, a, a, n, c, v, a, None)
+            assert rc == 1 and lib.hdf_last_error().startswith(b"dice:"), (what, rc, lib.hdf_last_error())
+            for accumulate in (0, 1):
+                rc = lib.hdf_confusion_matrix(dtype, a, a, n, c, v, a, accumulate, None)
+                assert rc == 1 and lib.hdf_last_error().startswith(b"confusion:"), (what, rc, lib.hdf_last_error())
+
+
 def test_dropin_module_surface():
     from models.HDenseFormer import HDenseFormer, HDenseFormer_16, HDenseFormer_32
     net = HDenseFormer_16(in_channels=2, n_cls=3, image_size=(32, 32, 32), transformer_depth=8)

@@ -182,7 +182,7 @@ def test_autocast_selects_bf16_and_backward_runs():
 
 
 @pytest.mark.parametrize("tag", ["c3", "c4", "c4_absent"])
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 def test_fused_loss_vs_reference_golden(tag, dt):
     from loss.combine_loss import CEPlusDice, DeepSuperloss
     g = np.load(os.path.join(GOLDEN, "g3_loss.npz"))
@@ -198,7 +198,7 @@ def test_fused_loss_vs_reference_golden(tag, dt):
 
 
 @pytest.mark.parametrize("tag", ["deep_w", "cepd_w", "dice_w", "dice_all", "dice_w_all", "ce_w"])
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 def test_weighted_loss_forms_vs_reference_golden(tag, dt):
     """What trainer.py:743-771 builds with a class_weight list (and DiceLoss(ignore_index=None)), through the drop-in
     loss modules, against fixtures from the reference's own classes (oracle/make_goldens.py --only g3w)."""
