@@ -1,11 +1,12 @@
 // Process state (last error, compute-unit budget) and the one-to-one C ABI wrappers of the operator launchers: losses,
-// metrics, normalisation, sliding window, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
+// metrics, normalisation, sliding window, augmentation, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
 #include <atomic>
 #include <algorithm>
 #include <cstdarg>
 #include <cstring>
 
 #include "../../include/hdf.h"
+#include "augment.h"
 #include "conv_igemm.h"
 #include "loss.h"
 #include "optim.h"
@@ -168,6 +169,15 @@ int hdf_onehot_from_labels(const uint8_t* labels, float* onehot, int batch, int 
                            hdf_stream stream) {
   HDF_CHECK_ARG(labels && onehot, "onehot_from_labels: null argument");
   return hdf_launch_onehot(labels, onehot, batch, n_cls, voxels, (hipStream_t)stream);
+}
+int hdf_augment_3d(const float* image, const uint8_t* labels, int channels, int n_cls, int D, int H, int W,
+                   const double* affine, int flip_h, int flip_w, float* image_out, uint8_t* labels_out, float* onehot_out,
+                   hdf_stream stream) {
+  HDF_CHECK_ARG(affine, "augment_3d: null affine");
+  AugAffine a;
+  std::memcpy(a.m, affine, sizeof(a.m));   // read during the call: the caller may reuse the array at once
+  return hdf_launch_augment3d(image, labels, channels, n_cls, D, H, W, a, flip_h, flip_w, image_out, labels_out,
+                              onehot_out, (hipStream_t)stream);
 }
 int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,

@@ -1,0 +1,13 @@
+#pragma once
+#include "hdf_common.h"
+
+// [A | t] of RandomTranslationRotationZoom3D, row-major 3x4, passed to the kernel by value
+struct AugAffine {
+  double m[12];
+};
+
+// one training sample through warp + flip (+ one-hot): image [C][D][H][W] fp32, labels [D][H][W] uint8 (null when
+// neither label output is asked for); every output may be null.  data_utils/transformer_3d.py:45-169
+int hdf_launch_augment3d(const float* image, const uint8_t* labels, int C, int n_cls, int D, int H, int W,
+                         const AugAffine& aff, int flip_h, int flip_w, float* image_out, uint8_t* labels_out,
+                         float* onehot_out, hipStream_t st);

@@ -1,2 +1,16 @@
 """Runtime of the MI355X-native H-DenseFormer hot path (ctypes over libhdf_hip.so)."""
 from ._lib import BF16, F32, EXPORTS, HdfError, LIB_PATH, lib  # noqa: F401
+
+_AUGMENT = ("TrainTransform3D", "augment_3d", "crop_origin", "flip_flags", "trz_matrix")
+
+
+def __getattr__(name):
+    # `from hdf_rt import augment_3d` works, but `import hdf_rt` alone still loads neither torch nor numpy
+    if name in _AUGMENT:
+        from . import augment
+        return getattr(augment, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def __dir__():
+    return sorted(list(globals()) + list(_AUGMENT))

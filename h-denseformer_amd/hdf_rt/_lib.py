@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("HDF_LIB_PATH") or os.path.join(os.path.dirname(_HERE)
 F32, BF16, F16 = 0, 1, 2
 
 _vp, _i, _i64, _f, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
+_pd = C.POINTER(C.c_double)
 
 _PROTOS = {
     "hdf_version": (C.c_char_p, []),
@@ -64,6 +65,7 @@ _PROTOS = {
     "hdf_sw_accumulate": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "hdf_sw_finalize": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
     "hdf_onehot_from_labels": (_i, [_vp, _vp, _i, _i, _i64, _vp]),
+    "hdf_augment_3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _pd, _i, _i, _vp, _vp, _vp, _vp]),
     "hdf_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _vp]),
     "hdf_optim_step": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp, _vp]),
     "hdf_op_to_channels_last": (_i, [_i, _vp, _vp, _i, _i, _i, _i64, _vp]),

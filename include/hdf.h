@@ -251,6 +251,26 @@ int hdf_sw_finalize(const float* prob_sum, const float* count, int n_cls, int64_
 int hdf_onehot_from_labels(const uint8_t* labels, float* onehot, int batch, int n_cls, int64_t voxels,
                            hdf_stream stream);
 
+/* ---- training augmentation of one sample on the device: RandomTranslationRotationZoom3D, RandomFlip3D and To_Tensor
+ * (data_utils/transformer_3d.py:45-169, data_utils/data_loader.py:126-159) in one launch.
+ * image [channels][D][H][W] fp32 and labels [D][H][W] uint8, both contiguous.  For output voxel p = (d, h, w) -- with
+ * h -> H-1-h when flip_h and w -> W-1-w when flip_w, i.e. the flip follows the warp -- the source coordinate is
+ * c = A (p - s) + t + s, s = (D/2, H/2, W/2), [A | t] = affine: 12 doubles on the HOST, row-major 3x4, read during the
+ * call.  Interpolation is what skimage.transform.warp does on a 3-D array since release 0.19:
+ * scipy.ndimage.map_coordinates(order=1, mode='grid-constant', cval=0), trilinear on the volume zero-padded to infinity
+ * (a corner outside contributes 0; a coordinate in (-1, 0) blends the edge voxel with 0), accumulated in fp64 and
+ * rounded once to fp32.  warp's clip=True is not applied (a no-op here whenever a channel's range contains 0).
+ * Labels (transformer_3d.py:113-116): for z = 1 .. n_cls-1 ascending, the interpolated (label == z) mask is compared
+ * with `>= 0.5` (inclusive) in fp64 and the LAST class that reaches it wins, else 0; label values >= n_cls match no
+ * class and act as background.
+ * Outputs, each written when non-null: image_out [channels][D][H][W], labels_out [D][H][W] uint8, onehot_out
+ * [n_cls][D][H][W] fp32 in the To_Tensor layout of hdf_onehot_from_labels.  labels may be null only when both label
+ * outputs are null (image likewise when image_out is null).  No output may overlap a source.  channels 1..64,
+ * n_cls 2..8, every dimension >= 1. */
+int hdf_augment_3d(const float* image, const uint8_t* labels, int channels, int n_cls, int D, int H, int W,
+                   const double* affine, int flip_h, int flip_w, float* image_out, uint8_t* labels_out, float* onehot_out,
+                   hdf_stream stream);
+
 /* ---- optimizer: torch.optim.Adam as configured by trainer.py:793-840 (L2 weight decay on the mask) ---- */
 int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,

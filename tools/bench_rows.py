@@ -2,6 +2,7 @@
 bounded host-side restatement of what the reference does for the same call (numpy / torch CPU on this box's cores).
 
   python tools/bench_rows.py > profiles/<round>_rows.json      (one JSON object per line)
+  python tools/bench_rows.py augment                            (the augmentation row alone)
 """
 import json
 import os
@@ -48,6 +49,47 @@ def cpu_s(fn, reps=3):
 def emit(**kw):
     print(json.dumps(kw), flush=True)
 
+
+def augment_row(C=4, n_cls=4, S=128):
+    """hdf_augment_3d on one 4x128^3 sample, all three outputs, next to two streaming yardsticks that move the same bytes
+    in the same run: hdf_onehot_from_labels on the sample's voxels plus a device copy of the image"""
+    from hdf_rt import augment_3d, trz_matrix
+    gen = torch.Generator().manual_seed(11)
+    V = S ** 3
+    img = torch.randn(C, S, S, S, generator=gen).to(DEV)
+    lab_h = torch.randint(0, n_cls, (S, S, S), generator=gen, dtype=torch.uint8)
+    lab1 = lab_h.to(DEV)
+    aff = trz_matrix("tr", np.random.RandomState(11))
+    o_img, o_oh, o_lab = torch.empty_like(img), torch.empty((n_cls, S, S, S), device=DEV), torch.empty_like(lab1)
+    us = 1e3 * gpu_ms(lambda: augment_3d(img, lab1, n_cls, aff, True, False, o_img, o_oh, o_lab), reps=30, warm=5)
+    us_oh = 1e3 * gpu_ms(lambda: inference.onehot_from_labels(lab1[None], n_cls), reps=30, warm=5)
+    us_cp = 1e3 * gpu_ms(lambda: o_img.copy_(img), reps=30, warm=5)
+    by = (4 * C + 1 + 4 * C + 4 * n_cls + 1) * V
+    try:
+        from scipy.ndimage import map_coordinates
+        p = np.mgrid[:S, :S, :S].astype(np.float64) - S / 2
+        coords = np.einsum("ij,jdhw->idhw", aff[:, :3], p) + aff[:, 3, None, None, None] + S / 2
+        img_np, lab_np = img.cpu().numpy(), lab_h.numpy()
+
+        def ref_chain():   # transformer_3d.py:108-117: one warp per channel and one per foreground class
+            for ch in img_np:
+                map_coordinates(ch, coords, order=1, mode="grid-constant", cval=0, prefilter=False)
+            for z in range(1, n_cls):
+                map_coordinates((lab_np == z).astype(np.float32), coords, order=1, mode="grid-constant", cval=0, prefilter=False)
+
+        cpu = {"kind": "port", "what": f"scipy.ndimage.map_coordinates order 1, {C + n_cls - 1} warps of {S}^3 (transformer_3d.py:108-117)",
+               "s_per_sample": cpu_s(ref_chain, reps=1), "threads": 1}
+    except ImportError as exc:
+        cpu = {"kind": "not measured", "what": repr(exc)}
+    emit(row="augment_3d", config=f"{C}x{S}^3 fp32 + uint8 labels, n_cls {n_cls}, mode 'tr' + H flip, image + labels + one-hot out",
+         gpu_us=us, algorithmic_bytes=by, achieved_GBps=by / us / 1e3, hbm_peak_GBps=8000,
+         yardstick_us={"onehot_from_labels": us_oh, "image_copy": us_cp}, ratio_to_yardsticks=us / (us_oh + us_cp),
+         cpu_baseline=cpu)
+
+
+if sys.argv[1:] == ["augment"]:
+    augment_row()
+    sys.exit(0)
 
 g = torch.Generator().manual_seed(7)
 B, C, S = 2, 4, 128
@@ -106,6 +148,8 @@ emit(row="8f-3 mr_normalize_", config=f"{C}x{S}^3 fp32 in place (clone time {ms0
      algorithmic_bytes=by, achieved_GBps=by / max(ms - ms0, 1e-6) / 1e6, hbm_peak_GBps=8000,
      cpu_baseline={"kind": "port", "what": "numpy per-channel min/max rescale of the same volume", "s_per_sample": cpu_s(ref_mr),
                    "threads": 1})
+
+augment_row()
 
 # ---- 8f-2: sliding-window inference
 from models.HDenseFormer import HDenseFormer
