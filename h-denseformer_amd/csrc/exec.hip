@@ -1,194 +1,48 @@
 // The executor: the forward / backward launch sequences of HDenseFormer.forward (HDenseFormer.py:229-255) and its
-// autograd over a plan (plan.hip), and the stream ordering between them.
+// autograd over a plan (plan.hip), around the transformer branches' own sequences (exec_tf.hip).
 #include <algorithm>
-#include <cstring>
-#include <map>
-#include <string>
 
-#include "plan_internal.h"
-#include "loss.h"
-#include "transformer.h"
+#include "exec_internal.h"
 #include "unet_ops.h"
 
 namespace {
 
-// A non-blocking stream at the highest / lowest priority the device offers (an unprioritised one where priorities are not
-// to be had); nullptr: no stream.  The plan's branch (highest) and side (lowest) streams.
-hipStream_t make_stream(bool highest) {
-  hipStream_t s = nullptr;
-  int least = 0, greatest = 0;
-  if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
-      hipStreamCreateWithPriority(&s, hipStreamNonBlocking, highest ? greatest : least) != hipSuccess) {
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) s = nullptr;
-  }
-  return s;
+// The launch block of a 3x3x3 convolution `in` (Cin channels) -> `out` (Cout channels) with the packed weights at workspace
+// offset `w`: stride 1, stride 2 or transposed by the levels the two views live at.  The callers add what differs (bias,
+// Xf, statistics table, bs_*, split, budget, priority).
+ConvArgs conv_args(const Exec& e, const View& in, int Cin, const View& out, int Cout, size_t w, int wfrag) {
+  const int *di = e.dm(in.lvl), *dO = e.dm(out.lvl);
+  ConvArgs a{};
+  a.in = e.at(in), a.in_pitch = in.pitch, a.Cin = Cin;
+  a.N = e.B;
+  a.Di = di[0], a.Hi = di[1], a.Wi = di[2];
+  a.Do = dO[0], a.Ho = dO[1], a.Wo = dO[2];
+  a.w = e.ws + w, a.wfrag = wfrag;
+  a.out = e.at(out), a.out_pitch = out.pitch, a.Cout = Cout, a.CoutP = round_up(Cout, 32);
+  return a;
 }
-
-// Backward runs its weight gradients on the plan's side stream.  They are off the critical path (nothing in backward
-// reads a weight gradient), MFMA-bound, and leave wave slots and 50 KB of LDS per CU free, while the chain they would
-// otherwise delay is full of HBM-bound passes (InstanceNorm backward, pooling / up-sampling backward, heads): with both in
-// flight the memory-bound kernels run under the matrix kernels (tools/overlap_probe.py: a 64->32 weight gradient plus
-// three elementwise passes over 268 MB tensors take 708 us on two streams against 880 us back to back).  Ordering:
-//  * fork: the side stream waits for an event recorded on the main stream after the producers of the operands;
-//  * a buffer a side-stream kernel still reads (the dy of a conv) is not overwritten: wait_readers() before its next
-//    writer on the main stream (each level keeps two dy buffers so that the wait is normally already satisfied);
-//  * join: the main stream waits for the side stream's last event at the end of every backward call, so at the ABI
-//    boundary all work is ordered on the caller's stream as before.
-// The shared weight-gradient workspace is only touched on the side stream (its kernels run in order).
-struct Exec {
-  hdf_plan* p;
-  char* ws;
-  const float* params;
-  float* grads;
-  int B;
-  hipStream_t st;
-  int conv_budget = 0;                          // ConvArgs::cu_budget of the convolutions issued through this Exec (0: all)
-  bool async = false;                           // weight gradients on the side stream
-  bool on_branch = false;                       // this Exec issues onto the plan's branch stream (own scratch)
-  hipEvent_t last_side = nullptr;               // last event recorded on the side stream in this call
-  hipEvent_t tf_packed = nullptr;               // branch Exec: the persistent transformer kernel's weight copies are ready (forward3d)
-  std::map<size_t, hipEvent_t> readers;         // workspace offset of a buffer -> side-stream event after its last reader
-  hipEvent_t next_event() {
-    if (p->events.size() < 256) {
-      hipEvent_t ev = nullptr;
-      if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return nullptr;
-      p->events.push_back(ev);
-      return ev;
-    }
-    return p->events[p->ev_next++ % p->events.size()];
-  }
-  // Stream ordering, all of it: a fresh ring event recorded on `from` that `to` waits for (wait = false: recorded only, for
-  // a waiter that comes later).  Returns the event; nullptr: no event, or the record / the wait failed.  What that means
-  // is the caller's decision: where it is an error (HDF_ERR_HIP) the caller names the `roles` for the message ("<waiting
-  // stream> behind <recorded stream>"), where there is a fallback it does not.
-  hipEvent_t order(hipStream_t from, hipStream_t to, const char* roles = nullptr, bool wait = true) {
-    hipEvent_t ev = next_event();
-    if (ev && hipEventRecord(ev, from) == hipSuccess && (!wait || hipStreamWaitEvent(to, ev, 0) == hipSuccess)) return ev;
-    if (roles) hdf_set_error("stream ordering failed (event record / wait): %s", roles);
-    return nullptr;
-  }
-  // `to` waits for an event recorded earlier
-  int wait(hipStream_t to, hipEvent_t ev, const char* roles) {
-    if (hipStreamWaitEvent(to, ev, 0) == hipSuccess) return HDF_OK;
-    hdf_set_error("stream ordering failed (event wait): %s", roles);
-    return HDF_ERR_HIP;
-  }
-  // stream for a weight-gradient launch whose operands are ready on the main stream now
-  hipStream_t wgrad_stream() {
-    if (!async) return st;
-    if (!order(st, p->side)) {
-      // fall back to in-order execution: first order this stream behind EVERYTHING the side stream holds -- the main and
-      // the branch Exec both feed it and share the one weight-gradient workspace this stream is about to reuse, so this
-      // Exec's own last_side is not enough.  A fresh event on the side stream, or, if events are what fails, a host wait.
-      if (!order(p->side, st)) (void)hipStreamSynchronize(p->side);
-      last_side = nullptr;
-      readers.clear();
-      async = false;
-      return st;
-    }
-    return p->side;
-  }
-  // after the launch: remember that `buf` is read on the side stream until now
-  // (an event that cannot be recorded would leave the launch outside every later join: a hard error, not a silent
-  // loss of ordering)
-  int wgrad_done(const View& buf) { return side_done(&buf); }
-  // buf == nullptr: the same for a side-stream launch whose operands are never overwritten inside this call: only join()
-  // waits for it
-  int side_done(const View* buf = nullptr) {
-    if (!async) return HDF_OK;
-    hipEvent_t d = order(p->side, st, nullptr, false);
-    if (!d) {
-      (void)hipStreamSynchronize(p->side);
-      hdf_set_error("backward: could not record the side stream's completion event");
-      return HDF_ERR_HIP;
-    }
-    last_side = d;
-    if (buf) readers[buf->off] = d;
-    return HDF_OK;
-  }
-  void wait_readers(const View& buf) {
-    auto it = readers.find(buf.off);
-    if (it != readers.end()) {
-      (void)hipStreamWaitEvent(st, it->second, 0);
-      readers.erase(it);
-    }
-  }
-  void join() {
-    if (last_side) (void)hipStreamWaitEvent(st, last_side, 0);
-    last_side = nullptr;
-    readers.clear();
-  }
-  // scratch of this Exec's stream (two streams of one call must not share the per-launch partial-sum tables)
-  float* statp() const { return f(on_branch ? p->stat_partials2 : p->stat_partials); }
-  float* kspl() const { return f(on_branch ? p->ksplit_ws2 : p->ksplit_ws); }
-  float* inbp() const { return f(on_branch ? p->inb_partials2 : p->inb_partials); }
-  float* inbk() const { return f(on_branch ? p->inb_k2 : p->inb_k); }
-  // fork: a second Exec on the plan's branch stream, ordered behind everything issued on this one so far.  nullptr
-  // stream when the branch stream cannot be used (creation / event failure): the caller then stays in order.
-  hipStream_t fork_branch() {
-    if (!p->branch) p->branch = make_stream(true);  // the branch carries the longer dependency chain: highest priority
-    if (!p->branch) return nullptr;
-    return order(st, p->branch) ? p->branch : nullptr;
-  }
-  // join a branch Exec back: this stream waits for everything issued on the branch (incl. its side-stream work)
-  int join_branch(Exec& b) {
-    b.join();
-    return order(b.st, st, "the forking stream behind the branch stream (join)") ? HDF_OK : HDF_ERR_HIP;
-  }
-  void* at(const View& v) const { return ws + v.off; }
-  float* f(size_t off) const { return reinterpret_cast<float*>(ws + off); }
-  const float* P(int64_t off) const { return off < 0 ? nullptr : params + off; }
-  float* G(int64_t off) const { return off < 0 ? nullptr : grads + off; }
-  const int* dm(int lvl) const { return p->dims[lvl]; }
-};
-
-// Every return path of a forward / backward call (also the HDF_TRY error returns) orders the branch stream (while `forked`)
-// and the side stream behind the caller's stream: the caller may free or reuse the workspace / gradient buffers as soon as
-// its own stream gets there.  (A forward has nothing on the side stream: its e.join() issues nothing.)
-struct Rejoin {
-  Exec &e, &eb;
-  bool forked;
-  ~Rejoin() {
-    if (forked) (void)e.join_branch(eb);
-    e.join();
-  }
-};
-
-// per-(n,c) input transform of a consumer: the producer's InstanceNorm scale/shift (+ReLU)
-struct Xf {
-  const float* scale = nullptr;
-  const float* shift = nullptr;
-  int relu = 0;
-};
-Xf xf_of(const Exec& e, const Conv3& c) { return Xf{e.f(c.st.scale), e.f(c.st.shift), 1}; }
+// the same for a weight gradient: `sm` (SC channels) is the tensor at the lower or equal resolution
+WgradArgs wgrad_args(const Exec& e, const View& sm, int SC, const View& lg, int LC) {
+  const int *ds = e.dm(sm.lvl), *dl = e.dm(lg.lvl);
+  WgradArgs w{};
+  w.sm = e.at(sm), w.sm_pitch = sm.pitch, w.SC = SC;
+  w.lg = e.at(lg), w.lg_pitch = lg.pitch, w.LC = LC;
+  w.N = e.B;
+  w.Ds = ds[0], w.Hs = ds[1], w.Ws = ds[2];
+  w.Dl = dl[0], w.Hl = dl[1], w.Wl = dl[2];
+  return w;
+}
 
 // probe: record the plan's probe events immediately around the convolution launch (hdf_plan_set_probe)
 int conv_forward(Exec& e, Conv3& c, const View& in, Xf xf, bool probe = false) {
   hdf_plan* p = e.p;
   const int* d = e.dm(c.lvl);
-  const int CoutP = round_up(c.Cout, 32);
-  ConvArgs a{};  // weights: packed by hdf_forward's pack batch
+  ConvArgs a = conv_args(e, in, c.CinP, c.y, c.Cout, c.wf, c.wf_frag);  // weights: packed by hdf_forward's pack batch
   a.prio = e.on_branch;  // the UpConv chain's convolutions run next to the encoder's persistent ones (ConvArgs::prio)
   a.cu_budget = e.conv_budget;
-  a.in = e.at(in);
-  a.in_pitch = in.pitch;
-  a.Cin = c.CinP;
-  a.N = e.B;
-  a.Di = a.Do = d[0];
-  a.Hi = a.Ho = d[1];
-  a.Wi = a.Wo = d[2];
-  a.w = e.ws + c.wf;
-  a.wfrag = c.wf_frag;
   a.bias = e.P(c.b);
-  a.in_scale = xf.scale;
-  a.in_shift = xf.shift;
-  a.in_relu = xf.relu;
-  a.out = e.at(c.y);
-  a.out_pitch = c.y.pitch;
-  a.Cout = c.Cout;
-  a.CoutP = CoutP;
+  a.in_scale = xf.scale, a.in_shift = xf.shift, a.in_relu = xf.relu;
   a.stat_partials = e.statp();
-  a.accumulate = 0;
   a.kpart = e.kspl(), a.kpart_bytes = HDF_KSPLIT_BYTES;
   // the encoder's first layer (<= 4 real channels in a 16-channel row): K = (tap, channel), csrc/conv_first.hip
   if (c.Cin <= 4 && !xf.scale && hdf_conv_first_takes(p->dtype, c.Cin, c.Cout, d[0], d[1], d[2], in.pitch)) {
@@ -207,34 +61,17 @@ int conv_forward(Exec& e, Conv3& c, const View& in, Xf xf, bool probe = false) {
     }
   }
   int tiles = hdf_conv_stat_tiles(0, d[0], d[1], d[2], c.CinP * p->esz);
-  HDF_TRY(hdf_launch_in_finalize(e.statp(), e.B, tiles, c.Cout, CoutP, p->vox(c.lvl), e.P(c.gamma),
+  HDF_TRY(hdf_launch_in_finalize(e.statp(), e.B, tiles, c.Cout, a.CoutP, p->vox(c.lvl), e.P(c.gamma),
                                  e.P(c.beta), 1e-5f, e.f(c.st.mean), e.f(c.st.rstd), e.f(c.st.scale),
                                  e.f(c.st.shift), e.st));
   return HDF_OK;
 }
 
 int convt_forward(Exec& e, ConvT3& t, const View& in, Xf xf, const View& out) {
-  hdf_plan* p = e.p;
-  const int* d = e.dm(t.lvl_in);
-  const int CoutP = round_up(t.Cout, 32);
-  ConvArgs a{};
-  a.in = e.at(in);
-  a.in_pitch = in.pitch;
-  a.Cin = t.Cin;
-  a.N = e.B;
-  a.Di = d[0], a.Hi = d[1], a.Wi = d[2];
-  a.Do = (p->flat ? 1 : 2) * d[0], a.Ho = 2 * d[1], a.Wo = 2 * d[2];
-  a.w = e.ws + t.wf;
-  a.wfrag = t.wf_frag;
+  ConvArgs a = conv_args(e, in, t.Cin, out, t.Cout, t.wf, t.wf_frag);
   a.bias = e.P(t.b);
-  a.in_scale = xf.scale;
-  a.in_shift = xf.shift;
-  a.in_relu = xf.relu;
-  a.out = e.at(out);
-  a.out_pitch = out.pitch;
-  a.Cout = t.Cout;
-  a.CoutP = CoutP;
-  return hdf_launch_conv(p->dtype, 2, a, e.st);
+  a.in_scale = xf.scale, a.in_shift = xf.shift, a.in_relu = xf.relu;
+  return hdf_launch_conv(e.p->dtype, 2, a, e.st);
 }
 
 int head_forward(Exec& e, const Head1& h, const View& in, Xf xf, void* out) {
@@ -242,309 +79,27 @@ int head_forward(Exec& e, const Head1& h, const View& in, Xf xf, void* out) {
                              e.p->ncls, e.p->vox(h.lvl), e.st);
 }
 
-TfDims tf_dims(const hdf_plan* p, int B) {
-  TfDims d;
-  d.M = p->M;
-  d.B = B;
-  d.N = p->Ntok;
-  d.DM = p->DM;
-  d.DMF = p->DMF;
-  d.mstride = p->mstride;
-  d.training = p->training;
-  d.seed = p->seed;
-  d.thresh24 = 1u << 23;  // p = 0.5 (HDenseFormer.py:79,105)
-  d.keep_scale = 2.0f;
-  return d;
-}
-
-void tf_layer_ptrs(const hdf_plan* p, float* base, int b, int l, TfLayerP& q) {
-  std::string pre = "attns.0.blocks." + std::to_string(b) + ".0.layers." + std::to_string(l);
-  q.w0 = base + p->P(pre + ".0.weight");
-  q.b0 = base + p->P(pre + ".0.bias");
-  q.ln1g = base + p->P(pre + ".1.norm.weight");
-  q.ln1b = base + p->P(pre + ".1.norm.bias");
-  q.wqkv = base + p->P(pre + ".1.fn.to_qkv.weight");
-  q.wout = base + p->P(pre + ".1.fn.to_out.0.weight");
-  q.bout = base + p->P(pre + ".1.fn.to_out.0.bias");
-  q.ln2g = base + p->P(pre + ".2.norm.weight");
-  q.ln2b = base + p->P(pre + ".2.norm.bias");
-  q.w1 = base + p->P(pre + ".2.fn.net.0.weight");
-  q.b1 = base + p->P(pre + ".2.fn.net.0.bias");
-  q.w2 = base + p->P(pre + ".2.fn.net.3.weight");
-  q.b2 = base + p->P(pre + ".2.fn.net.3.bias");
-}
-void tf_out_ptrs(const hdf_plan* p, float* base, int b, TfOutP& q) {
-  std::string pre = "attns.0.blocks." + std::to_string(b) + ".0.out_layer.net";
-  q.wa = base + p->P(pre + ".0.weight");
-  q.ba = base + p->P(pre + ".0.bias");
-  q.wb = base + p->P(pre + ".3.weight");
-  q.bb = base + p->P(pre + ".3.bias");
-}
-TfLayerSave tf_save(const hdf_plan* p, const Exec& e, int b, int l) {
-  const int64_t rows = (int64_t)p->M * e.B * p->Ntok;
-  float* base = e.f(p->tf_save) + (int64_t)(b * 4 + l) * rows * 232;
-  TfLayerSave s;
-  s.h0 = base;
-  s.qkv = base + rows * 32;
-  s.ob = base + rows * 128;
-  s.lse = base + rows * 160;
-  s.h1 = base + rows * 168;
-  s.h2 = base + rows * 200;
-  return s;
-}
-
-// Parameter addressing of the persistent transformer kernels (TfChainP, transformer.h): block-relative offsets of the 13
-// tensors of each of a block's four dense layers and of its out_layer, the same for every block and modality.
-TfChainP tf_chain_params(const hdf_plan* p) {
-  TfChainP c{};
-  c.blk0 = p->P("attns.0.blocks.0.0.layers.0.0.weight");
-  c.blk_stride = p->nb > 1 ? p->P("attns.0.blocks.1.0.layers.0.0.weight") - c.blk0 : 0;
-  TfLayerP q;
-  TfOutP o;
-  float* base = nullptr;
-  for (int l = 0; l < 4; l++) {
-    tf_layer_ptrs(p, base, 0, l, q);
-    float* const f[13] = {q.w0, q.b0, q.ln1g, q.ln1b, q.wqkv, q.wout, q.bout, q.ln2g, q.ln2b, q.w1, q.b1, q.w2, q.b2};
-    for (int k = 0; k < 13; k++) c.loff[l][k] = (int32_t)((f[k] - base) - c.blk0);
-  }
-  tf_out_ptrs(p, base, 0, o);
-  float* const g[4] = {o.wa, o.ba, o.wb, o.bb};
-  for (int k = 0; k < 4; k++) c.ooff[k] = (int32_t)((g[k] - base) - c.blk0);
-  return c;
-}
-// The persistent kernels take the plan's transformer when every 16-token tile of every sequence gets a compute unit of
-// its own (resident together: their per-sequence barriers need that).  HDF_NO_TF_CHAIN=1: the launch chain
-// (tok_fwd / attention / tok_bwd ...) instead -- the third arrangement knob of tests/test_gpu_knobs.py.
-// Decided ONCE per forward (forward3d stores the answer in p->tf_fwd_chain); the backward follows the forward it belongs
-// to instead of reading the environment again (a knob flipped between the two calls made the persistent
-// backward consume records the launch-chain forward never wrote).
-bool tf_use_chain(const hdf_plan* p, int B) {
-  const bool off = getenv("HDF_NO_TF_CHAIN") != nullptr;   // read per FORWARD call: tests switch it inside one process
-  if (off || p->chain_off) return false;
-  TfDims d = tf_dims(p, B);
-  return p->chain_forced ? tf_chain_shape_ok(d) : tf_chain_supported(d);
-}
-// the plan's host-mapped give-up word, created on first use
-int chain_flag_ensure(hdf_plan* p) {
-  if (p->chain_flag) return HDF_OK;
-  void* h = nullptr;
-  if (hipHostMalloc(&h, 64, hipHostMallocMapped) != hipSuccess) {
-    hdf_set_error("transformer chain: could not allocate the host-mapped status word");
-    return HDF_ERR_HIP;
-  }
-  void* dv = nullptr;
-  if (hipHostGetDevicePointer(&dv, h, 0) != hipSuccess) {
-    (void)hipHostFree(h);
-    hdf_set_error("transformer chain: no device address for the host-mapped status word");
-    return HDF_ERR_HIP;
-  }
-  memset(h, 0, 64);
-  p->chain_flag = reinterpret_cast<unsigned*>(h);
-  p->chain_flag_dev = reinterpret_cast<unsigned*>(dv);
-  return HDF_OK;
-}
-// Called at the top of every forward / backward: a persistent launch of an EARLIER call gave up at a barrier (the device
-// was shared: its grid was not resident together within the deadline).  That call's outputs are NaN-poisoned garbage; this
-// call reports it once -- HDF_ERR_CHAIN_TIMEOUT, nothing launched -- and the plan runs the launch chain from now on.
-// (Asynchronous by nature: the host is ahead of the device, so the report can be one or more calls late; a caller that
-// synchronises can ask at once with hdf_plan_chain_state.)
-int chain_flag_check(hdf_plan* p) {
-  if (!p->chain_flag) return HDF_OK;
-  const unsigned v = __atomic_load_n(p->chain_flag, __ATOMIC_ACQUIRE);
-  if (v == 0) return HDF_OK;
-  __atomic_store_n(p->chain_flag, 0u, __ATOMIC_RELEASE);
-  p->chain_last_giveup = v;
-  p->chain_off = true;
-  hdf_set_error("persistent transformer kernel: workgroup %u gave up at a per-sequence barrier (the compute units were not "
-                "all available to the launch); the outputs of that call are NaN; this plan uses the launch chain from now on",
-                v - 1);
-  return HDF_ERR_CHAIN_TIMEOUT;
-}
-TfChainCtl chain_ctl(const hdf_plan* p) {
-  TfChainCtl c;
-  c.host_flag = p->chain_flag_dev;
-  c.ticks = p->chain_ticks;
-  return c;
-}
-
-int transformer_forward(Exec& e, const float* x) {
-  hdf_plan* p = e.p;
-  TfDims d = tf_dims(p, e.B);
-  float* pm = const_cast<float*>(e.params);
-  const int64_t rows = (int64_t)p->M * e.B * p->Ntok;
-  float* F0 = e.f(p->tf_F);
-  const int PE_LP = p->dtype;
-  // (flat: the 2-D input itself, depth 1, against depth slice 0 of the embedded 16^3 patch kernel)
-  HDF_TRY(tf_patch_embed_fwd(d, x, p->flat ? 1 : p->D, p->H, p->W, pm + p->P("attns.0.patch_embeddings.weight"),
-                             pm + p->P("attns.0.patch_embeddings.bias"), pm + p->P("attns.0.position_embeddings"), F0,
-                             e.st, PE_LP, p->flat ? 1 : 16));
-  if (p->tf_fwd_chain) {  // all layers of all blocks in one persistent launch (transformer_chain.hip)
-    if (e.tf_packed) HDF_TRY(e.wait(e.st, e.tf_packed, "the transformer's stream behind the weight packs"));
-    return tf_chain_forward(d, tf_chain_params(p), p->nb, pm, F0, e.f(p->tf_save), e.at(p->attnall),
-                            reinterpret_cast<unsigned*>(e.ws + p->tf_sync), e.ws + p->tf_wpack, e.f(p->tf_frag), p->dtype, e.st,
-                            chain_ctl(p));
-  }
-  // token kernel, attention, token kernel, ...: between two attention launches ONE kernel finishes the previous
-  // dense layer (and, at a block boundary, runs the block's out_layer) and starts the next one
-  TfLayerP prev{}, cur{};
-  TfOutP o{};
-  for (int b = 0; b < p->nb; b++) {
-    float* F = F0 + (int64_t)b * rows * p->DMF;
-    for (int l = 0; l < 4; l++) {
-      tf_layer_ptrs(p, pm, b, l, cur);
-      TfTokenFwd t;
-      if (l > 0) {
-        t.post = &prev, t.post_save = tf_save(p, e, b, l - 1), t.bp = b, t.lp = l - 1, t.F_post = F;
-      } else if (b > 0) {
-        float* Fp = F0 + (int64_t)(b - 1) * rows * p->DMF;
-        t.post = &prev, t.post_save = tf_save(p, e, b - 1, 3), t.bp = b - 1, t.lp = 3, t.F_post = Fp;
-        tf_out_ptrs(p, pm, b - 1, o);
-        t.out = &o, t.next_F = F;
-      }
-      t.pre = &cur, t.pre_save = tf_save(p, e, b, l), t.bq = b, t.lq = l, t.F_pre = F;
-      HDF_TRY(tf_token_fwd(d, t, p->dtype, e.st));
-      TfLayerSave s = tf_save(p, e, b, l);
-      HDF_TRY(tf_attention_fwd(d.N, d.M * d.B, s.qkv, s.ob, s.lse, e.st));
-      prev = cur;
-    }
-  }
-  TfTokenFwd t;
-  const int b = p->nb - 1;
-  t.post = &prev, t.post_save = tf_save(p, e, b, 3), t.bp = b, t.lp = 3, t.F_post = F0 + (int64_t)b * rows * p->DMF;
-  tf_out_ptrs(p, pm, b, o);
-  t.out = &o, t.attnall = e.at(p->attnall);
-  return tf_token_fwd(d, t, p->dtype, e.st);
-}
-
-int transformer_backward(Exec& e, const float* x) {
-  hdf_plan* p = e.p;
-  TfDims d = tf_dims(p, e.B);
-  float* pm = const_cast<float*>(e.params);
-  const int64_t rows = (int64_t)p->M * e.B * p->Ntok;
-  float* F0 = e.f(p->tf_F);
-  float* dF = e.f(p->tf_dF);
-  float* scratch = e.f(p->tf_scratch);
-  // token kernel, attention backward, token kernel, ...: one launch runs the Linear0 / LN1 / to_qkv backward of the
-  // layer whose attention backward just finished, (at a block boundary) the previous block's out_layer backward, and
-  // the ff / to_out backward of the next layer down
-  float* dO = scratch;
-  float* dh0acc = scratch + rows * 32;
-  float* dqkv = scratch + rows * 64;
-  // Every weight-matrix gradient of the branches comes from the tapes the token kernels leave behind (fixed-order
-  // reductions, no atomics): one launch per block, issued on the side stream as soon as that block's last tape segment
-  // is written (the token kernel that also starts the next block down), so that only block 0's -- next to the patch
-  // embedding's -- is left at the end of the chain.  (One launch for all blocks after the chain: 114 us with nothing
-  // else left to run beside it.)
-  TfWgradArgs w{};
-  {
-    const int64_t blk0 = p->P("attns.0.blocks.0.0.layers.0.0.weight");
-    const int64_t blk_stride = p->nb > 1 ? p->P("attns.0.blocks.1.0.layers.0.0.weight") - blk0 : 0;
-    int k = 0;
-    auto rel = [&](const std::string& n) { return p->P("attns.0.blocks.0.0." + n) - blk0; };
-    for (int l = 0; l < 4; l++) {
-      const std::string pre = "layers." + std::to_string(l);
-      w.e[k++] = TfWgradEntry{rel(pre + ".1.fn.to_qkv.weight"), 96, 32, l, 0, 0, TF_T_DQ, TF_T_T, -1, -1, 96, 32};
-      w.e[k++] = TfWgradEntry{rel(pre + ".0.weight"), 32, p->DM + 32 * l, l, 0, 1, TF_T_DH0, 0, -1, -1, 32, p->DMF};
-      w.e[k++] = TfWgradEntry{rel(pre + ".2.fn.net.3.weight"), 32, 64, l, 0, 0, TF_T_P1, TF_T_P1 + 32, TF_T_P0, TF_T_P0 + 32,
-                              32, 64};
-      w.e[k++] = TfWgradEntry{rel(pre + ".2.fn.net.0.weight"), 64, 32, l, 0, 0, TF_T_P1 + 96, TF_T_P1 + 160, TF_T_P0 + 96,
-                              TF_T_P0 + 160, 64, 32};
-      w.e[k++] = TfWgradEntry{rel(pre + ".1.fn.to_out.0.weight"), 32, 32, l, 0, 2, TF_T_DGO, 0, -1, -1, 32, 32};
-    }
-    w.e[k++] = TfWgradEntry{rel("out_layer.net.3.weight"), p->DM, 64, 0, 3, 3, 0, p->DM, -1, -1, p->DM, 64};
-    w.e[k++] = TfWgradEntry{rel("out_layer.net.0.weight"), 64, p->DMF, 0, 3, 1, p->DM + 64, 0, -1, -1, 64, p->DMF};
-    w.grads = e.grads, w.mstride = p->mstride, w.block0 = blk0, w.block_stride = blk_stride;
-    w.tape = e.f(p->tf_tape), w.otape = e.f(p->tf_otape), w.F = F0, w.save = e.f(p->tf_save);
-    w.rows = rows, w.BN = e.B * p->Ntok, w.DMF = p->DMF, w.b0 = 0;
-  }
-  auto wgrad_block = [&](int b) -> int {
-    w.b0 = b;
-    HDF_TRY(tf_wgrad(w, 1, p->M, e.wgrad_stream()));
-    return e.side_done();
-  };
-  p->tf_bwd_chain = p->tf_fwd_chain && tf_chain_backward_supported(d, p->dtype);
-  if (p->tf_bwd_chain) {
-    // one persistent launch for all layers (transformer_chain.hip); then every block's weight-matrix gradients from the
-    // tapes on the side stream, next to the patch embedding's backward on this one
-    HDF_TRY(tf_chain_backward(d, tf_chain_params(p), p->nb, pm, e.grads, F0, e.f(p->tf_save), dF, e.at(p->dAttnall),
-                              e.f(p->tf_tape), e.f(p->tf_otape), scratch, e.f(p->tf_frag), e.ws + p->tf_wpack,
-                              reinterpret_cast<unsigned*>(e.ws + p->tf_sync) + (1 << 17), p->dtype, e.st, chain_ctl(p)));
-    // (on this stream, not on the side stream: that one still holds the level-0 weight gradients, and tf_wgrad -- HBM-bound,
-    // 110 us -- would run behind them as the last kernel of the step)
-    HDF_TRY(tf_patch_embed_bwd(d, x, p->flat ? 1 : p->D, p->H, p->W, dF, e.grads + p->P("attns.0.patch_embeddings.weight"),
-                               e.grads + p->P("attns.0.patch_embeddings.bias"),
-                               e.grads + p->P("attns.0.position_embeddings"), scratch, e.st, p->flat ? 1 : 16));
-    w.b0 = 0;
-    HDF_TRY(tf_wgrad(w, p->nb, p->M, e.st));
-    return HDF_OK;
-  }
-  TfLayerP up{}, gup{}, cur{}, gcur{};
-  TfOutP o{}, go{};
-  bool have_up = false;
-  int ub = 0, ul = 0;
-  for (int b = p->nb - 1; b >= 0; b--) {
-    float* F = F0 + (int64_t)b * rows * p->DMF;
-    for (int l = 3; l >= 0; l--) {
-      tf_layer_ptrs(p, pm, b, l, cur);
-      tf_layer_ptrs(p, e.grads, b, l, gcur);
-      TfTokenBwd t;
-      t.dF = dF;
-      float* tape = e.f(p->tf_tape);
-      float* otape = e.f(p->tf_otape);
-      if (have_up) {
-        t.pre = &up, t.pre_grad = &gup, t.pre_save = tf_save(p, e, ub, ul), t.bq = ub, t.lq = ul;
-        t.F_pre = F0 + (int64_t)ub * rows * p->DMF, t.dqkv = dqkv, t.dh0acc = dh0acc;
-        if (tape) t.tape_pre = tape + (int64_t)(ub * 4 + ul) * rows * TF_TAPE_W;
-      }
-      if (l == 3) {
-        tf_out_ptrs(p, pm, b, o);
-        tf_out_ptrs(p, e.grads, b, go);
-        t.out = &o, t.out_grad = &go, t.bo = b, t.F_out = F;
-        if (!have_up) t.d_attnall = e.at(p->dAttnall);
-        if (otape) t.tape_out = otape + (int64_t)b * rows * p->DMF;
-      }
-      t.post = &cur, t.post_grad = &gcur, t.post_save = tf_save(p, e, b, l), t.bp = b, t.lp = l;
-      if (tape) t.tape_post = tape + (int64_t)(b * 4 + l) * rows * TF_TAPE_W;
-      t.dO = dO, t.dh0acc_out = dh0acc;
-      HDF_TRY(tf_token_bwd(d, t, p->dtype, e.st));
-      if (have_up && l == 3) HDF_TRY(wgrad_block(ub));  // block b + 1 is complete
-      TfLayerSave s = tf_save(p, e, b, l);
-      HDF_TRY(tf_attention_bwd(d.N, d.M * d.B, s.qkv, s.ob, s.lse, dO, dqkv, e.st, p->dtype));
-      up = cur, gup = gcur, ub = b, ul = l, have_up = true;
-    }
-  }
-  TfTokenBwd t;
-  t.dF = dF, t.pre = &up, t.pre_grad = &gup, t.pre_save = tf_save(p, e, 0, 0), t.bq = 0, t.lq = 0, t.F_pre = F0;
-  t.dqkv = dqkv, t.dh0acc = dh0acc;
-  t.tape_pre = e.f(p->tf_tape);
-  HDF_TRY(tf_token_bwd(d, t, p->dtype, e.st));
-  HDF_TRY(wgrad_block(0));
-  HDF_TRY(tf_patch_embed_bwd(d, x, p->flat ? 1 : p->D, p->H, p->W, dF, e.grads + p->P("attns.0.patch_embeddings.weight"),
-                             e.grads + p->P("attns.0.patch_embeddings.bias"),
-                             e.grads + p->P("attns.0.position_embeddings"), scratch, e.st, p->flat ? 1 : 16));
-  return HDF_OK;
-}
-
 // InstanceNorm(+ReLU) backward of conv layer c: da (grad w.r.t. the activation) -> dy (grad w.r.t. raw conv out)
-// pre_blocks > 0: the producer of da (head_backward) already wrote that many partial rows per sample
-// apply = false: only the statistics passes (k1 / ka / kb in e.inbk()); the consumer applies them itself
-// kbuf: where k1 | ka | kb go (default: the Exec's scratch, overwritten by its next in_backward)
-int in_backward(Exec& e, const Conv3& c, const View& da, const View& dy, int pre_blocks = 0, bool apply = true,
-                float* kbuf = nullptr) {
+struct InBwd {
+  int pre_blocks = 0;     // > 0: the producer of da already wrote that many partial rows per sample into e.inbp()
+  bool apply = true;      // false: only the statistics passes (k1 / ka / kb); the consumer applies them itself
+  float* kbuf = nullptr;  // where k1 | ka | kb go (default: the Exec's scratch, overwritten by its next in_backward)
+};
+int in_backward(Exec& e, const Conv3& c, const View& da, const View& dy, const InBwd& o = InBwd{}) {
   hdf_plan* p = e.p;
   const int64_t vox = p->vox(c.lvl);
-  const int blocks = pre_blocks > 0 ? pre_blocks : hdf_in_bwd_blocks(vox, c.Cout);
-  float* k = kbuf ? kbuf : e.inbk();
+  const int blocks = o.pre_blocks > 0 ? o.pre_blocks : hdf_in_bwd_blocks(vox, c.Cout);
+  float* k = o.kbuf ? o.kbuf : e.inbk();
   float* k1 = k;
   float* ka = k + (size_t)e.B * c.Cout;
   float* kb = k + (size_t)2 * e.B * c.Cout;
-  if (pre_blocks == 0)
+  if (o.pre_blocks == 0)
     HDF_TRY(hdf_launch_in_bwd_reduce(p->dtype, e.at(da), da.pitch, e.at(c.y), c.y.pitch, e.f(c.st.scale),
                                      e.f(c.st.shift), e.f(c.st.mean), e.f(c.st.rstd), e.inbp(), blocks, e.B,
                                      c.Cout, vox, e.st));
   HDF_TRY(hdf_launch_in_bwd_finalize(e.inbp(), blocks, e.B, c.Cout, vox, e.P(c.gamma), e.f(c.st.rstd), k1,
                                      ka, kb, e.G(c.gamma), e.G(c.beta), e.st));
-  if (!apply) return HDF_OK;
+  if (!o.apply) return HDF_OK;
   e.wait_readers(dy);  // a side-stream weight gradient may still read this buffer's previous contents
   HDF_TRY(hdf_launch_in_bwd_apply(p->dtype, e.at(da), da.pitch, e.at(c.y), c.y.pitch, e.f(c.st.scale), e.f(c.st.shift),
                                   e.f(c.st.mean), e.f(c.st.rstd), k1, ka, kb, e.at(dy), dy.pitch, e.B, c.Cout, vox,
@@ -552,37 +107,33 @@ int in_backward(Exec& e, const Conv3& c, const View& da, const View& dy, int pre
   return HDF_OK;
 }
 
-// conv backward: weight (and bias) gradient from (dy, input) and optionally the input gradient
-// din_colsum (optional, [colsum_C] floats): += the per-channel sums over (sample, voxel) of the first colsum_C channels of
-// the input gradient, taken from the dgrad conv's own InstanceNorm-partials epilogue (fp32 accumulators): the
-// ConvTranspose3d bias gradient of the layer that produced those channels, without a pass over the tensor
-// bs_next / bs_rows (optional): the conv whose InstanceNorm(+ReLU) backward consumes *din next.  Where the data-gradient
-// launch can (hdf_conv_bwd_stats_ok) its epilogue writes the first pass of that backward into e.inbp() and *bs_rows is
-// set to the rows per sample (pass it to in_backward as pre_blocks); else *bs_rows = 0.
-// ap (optional): dy has NOT been written yet.  ap->da is the gradient w.r.t. c's activation and in_backward(.., apply =
-// false) has left k1 | ka | kb at ap->k: the weight-gradient launch applies the second pass of the InstanceNorm backward to
-// the rows it stages and writes dy as it goes (WgradArgs::ap_*); this stream waits for it before the data gradient.
+// ap: dy has NOT been written yet.  ap->da is the gradient w.r.t. c's activation and in_backward(.., apply = false) has
+// left k1 | ka | kb at ap->k: the weight-gradient launch applies the second pass of the InstanceNorm backward to the rows it
+// stages and writes dy as it goes (WgradArgs::ap_*); this stream waits for it before the data gradient.
 struct InApply {
   const View* da;
   const float* k;
 };
+// conv backward: the weight gradient from (dy, input) and, with `din`, the input gradient.  Every field is optional.
+// din_colsum: taken from the dgrad conv's own InstanceNorm-partials epilogue (fp32 accumulators): the bias gradient of the
+// ConvTranspose3d that produced those channels, without a pass over the tensor.
+// bs_next / bs_rows: where the data-gradient launch can (hdf_conv_bwd_stats_ok) its epilogue writes the first pass of
+// bs_next's InstanceNorm(+ReLU) backward into e.inbp(); *bs_rows is then the next in_backward's pre_blocks, else 0.
+struct ConvBwd {
+  const View* din = nullptr;       // where the input gradient goes (null: none is computed)
+  int accumulate = 0;              // 1: it is added to *din
+  const View* din2 = nullptr;      // input channels [0, din->C) -> din, the rest -> din2 (two dense buffers of one pitch)
+  float* din_colsum = nullptr;     // += per-channel sums over (sample, voxel) of the input gradient's first ...
+  int colsum_C = 0;                // ... colsum_C channels
+  const Conv3* bs_next = nullptr;  // the conv whose InstanceNorm(+ReLU) backward consumes *din next
+  int* bs_rows = nullptr;          // <- rows per sample of that backward's first pass the data gradient left (0: none)
+  int pre_blocks = 0;              // norm_conv_backward: InBwd::pre_blocks of c's own InstanceNorm backward
+  const InApply* ap = nullptr;     // conv_backward: see InApply
+};
 // the weight-gradient launch of conv layer c (without the fused pass)
-static WgradArgs wgrad_args(Exec& e, const Conv3& c, const View& dy, const View& in, Xf xf) {
-  const int* d = e.dm(c.lvl);
-  WgradArgs w{};
-  w.sm = e.at(dy);
-  w.sm_pitch = dy.pitch;
-  w.SC = c.Cout;
-  w.lg = e.at(in);
-  w.lg_pitch = in.pitch;
-  w.LC = c.CinP;
-  w.N = e.B;
-  w.Ds = w.Dl = d[0];
-  w.Hs = w.Hl = d[1];
-  w.Ws = w.Wl = d[2];
-  w.lg_scale = xf.scale;
-  w.lg_shift = xf.shift;
-  w.lg_relu = xf.relu;
+static WgradArgs conv_wgrad_args(Exec& e, const Conv3& c, const View& dy, const View& in, Xf xf) {
+  WgradArgs w = wgrad_args(e, dy, c.Cout, in, c.CinP);
+  w.lg_scale = xf.scale, w.lg_shift = xf.shift, w.lg_relu = xf.relu;
   return w;
 }
 static void wgrad_args_apply(WgradArgs& w, Exec& e, const Conv3& c, const View& dy, const InApply& ap) {
@@ -596,12 +147,11 @@ static void wgrad_args_apply(WgradArgs& w, Exec& e, const Conv3& c, const View& 
   w.ap_tab[4] = ap.k, w.ap_tab[5] = ap.k + (size_t)e.B * c.Cout, w.ap_tab[6] = ap.k + (size_t)2 * e.B * c.Cout;
 }
 
-int conv_backward(Exec& e, Conv3& c, const View& dy, const View& in, Xf xf, const View* din, int accumulate,
-                  const View* din2 = nullptr, float* din_colsum = nullptr, int colsum_C = 0,
-                  const Conv3* bs_next = nullptr, int* bs_rows = nullptr, const InApply* ap = nullptr) {
+int conv_backward(Exec& e, Conv3& c, const View& dy, const View& in, Xf xf, const ConvBwd& o) {
   hdf_plan* p = e.p;
   const int* d = e.dm(c.lvl);
-  WgradArgs w = wgrad_args(e, c, dy, in, xf);
+  const InApply* ap = o.ap;  // (norm_conv_backward decides it)
+  WgradArgs w = conv_wgrad_args(e, c, dy, in, xf);
   if (ap) wgrad_args_apply(w, e, c, dy, *ap);
   // the encoder's first layer: K = (tap, channel) from the other side, csrc/conv_first.hip
   if (!ap && c.Cin <= 4 && !xf.scale &&
@@ -619,47 +169,34 @@ int conv_backward(Exec& e, Conv3& c, const View& dy, const View& in, Xf xf, cons
   // The norm subtracts the per-(sample, channel) mean, so dL/dbias = sum_voxels dy is identically zero (the reference
   // accumulates ~3e-8 of rounding noise there); the gradient buffer was zeroed at the start of backward,
   // so the four reduction passes over dy are simply not run.
-  if (din) {
+  if (o.din) {
     // dgrad = the same conv with taps reversed and channel roles swapped: Wd[t][ci][co] = W[co][ci][26-t]
-    const int OP = round_up(c.Cin, 32);
-    ConvArgs a{};
+    ConvArgs a = conv_args(e, dy, c.Cout, *o.din, c.Cin, c.wd, c.wd_frag);
     a.prio = e.on_branch;
-    a.in = e.at(dy);
-    a.in_pitch = dy.pitch;
-    a.Cin = c.Cout;
-    a.N = e.B;
-    a.Di = a.Do = d[0];
-    a.Hi = a.Ho = d[1];
-    a.Wi = a.Wo = d[2];
-    a.w = e.ws + c.wd;
-    a.wfrag = c.wd_frag;
-    a.out = e.at(*din);
-    a.out_pitch = din->pitch;
-    a.Cout = c.Cin;
-    a.CoutP = OP;
-    a.accumulate = accumulate;
-    if (din2) {  // input channels [0, din->C) -> din, the rest -> din2 (two dense buffers of one pitch)
-      a.out2 = e.at(*din2);
-      a.split = din->C;
+    a.accumulate = o.accumulate;
+    if (o.din2) {
+      a.out2 = e.at(*o.din2);
+      a.split = o.din->C;
     }
-    if (din_colsum) a.stat_partials = e.statp();  // forward scratch, free during backward
+    if (o.din_colsum) a.stat_partials = e.statp();  // forward scratch, free during backward
     a.kpart = e.kspl(), a.kpart_bytes = HDF_KSPLIT_BYTES;
-    if (bs_rows) *bs_rows = 0;
-    if (bs_next && bs_rows && !din_colsum && !din2) {
+    if (o.bs_rows) *o.bs_rows = 0;
+    if (o.bs_next && o.bs_rows && !o.din_colsum && !o.din2) {
+      const Conv3& n = *o.bs_next;
       ConvArgs b = a;
       b.stat_partials = e.inbp();
-      b.bs_y = e.at(bs_next->y), b.bs_y_pitch = bs_next->y.pitch;
-      b.bs_scale = e.f(bs_next->st.scale), b.bs_shift = e.f(bs_next->st.shift);
-      b.bs_mean = e.f(bs_next->st.mean), b.bs_rstd = e.f(bs_next->st.rstd);
-      if (bs_next->Cout == a.Cout && hdf_conv_bwd_stats_ok(p->dtype, b)) {
+      b.bs_y = e.at(n.y), b.bs_y_pitch = n.y.pitch;
+      b.bs_scale = e.f(n.st.scale), b.bs_shift = e.f(n.st.shift);
+      b.bs_mean = e.f(n.st.mean), b.bs_rstd = e.f(n.st.rstd);
+      if (n.Cout == a.Cout && hdf_conv_bwd_stats_ok(p->dtype, b)) {
         a = b;
-        *bs_rows = hdf_conv_stat_tiles(0, d[0], d[1], d[2], a.Cin * p->esz);
+        *o.bs_rows = hdf_conv_stat_tiles(0, d[0], d[1], d[2], a.Cin * p->esz);
       }
     }
     HDF_TRY(hdf_launch_conv(p->dtype, 0, a, e.st));
-    if (din_colsum) {
+    if (o.din_colsum) {
       const int rows = e.B * hdf_conv_stat_tiles(0, d[0], d[1], d[2], a.Cin * p->esz);
-      HDF_TRY(hdf_launch_stat_rows_sum(e.statp(), rows, colsum_C, OP, din_colsum, e.st));
+      HDF_TRY(hdf_launch_stat_rows_sum(e.statp(), rows, o.colsum_C, a.CoutP, o.din_colsum, e.st));
     }
   }
   return HDF_OK;
@@ -688,9 +225,7 @@ static int64_t fused_apply_min_vox() {
   }();
   return v;
 }
-int norm_conv_backward(Exec& e, Conv3& c, const View& da, const View& dy, int pre_blocks, const View& in, Xf xf,
-                       const View* din, int accumulate, const View* din2 = nullptr, float* din_colsum = nullptr,
-                       int colsum_C = 0, const Conv3* bs_next = nullptr, int* bs_rows = nullptr) {
+int norm_conv_backward(Exec& e, Conv3& c, const View& da, const View& dy, const View& in, Xf xf, ConvBwd o) {
   static const bool off = getenv("HDF_NO_FUSED_APPLY") != nullptr;  // A/B knob (tests/test_gpu_knobs.py)
   hdf_plan* p = e.p;
   const int* d = e.dm(c.lvl);
@@ -699,90 +234,50 @@ int norm_conv_backward(Exec& e, Conv3& c, const View& da, const View& dy, int pr
   if (fuse) {
     if (c.Cin <= 4 && !xf.scale && hdf_wgrad_first_takes(p->dtype, c.Cin, c.Cout, d[0], d[1], d[2], in.pitch, dy.pitch))
       fuse = false;  // the first layer's own kernel
-    WgradArgs w = wgrad_args(e, c, dy, in, xf);
+    WgradArgs w = conv_wgrad_args(e, c, dy, in, xf);
     wgrad_args_apply(w, e, c, dy, ap);
     fuse = fuse && hdf_wgrad_apply_takes(p->dtype, 1, w);
   }
-  HDF_TRY(in_backward(e, c, da, dy, pre_blocks, !fuse));
-  return conv_backward(e, c, dy, in, xf, din, accumulate, din2, din_colsum, colsum_C, bs_next, bs_rows,
-                       fuse ? &ap : nullptr);
+  InBwd ib;
+  ib.pre_blocks = o.pre_blocks, ib.apply = !fuse;
+  HDF_TRY(in_backward(e, c, da, dy, ib));
+  o.ap = fuse ? &ap : nullptr;
+  return conv_backward(e, c, dy, in, xf, o);
 }
 
 // ConvTranspose3d backward: dOut (hi-res) -> dIn (lo-res, grad w.r.t. the activation fed to the convT)
 int convt_backward(Exec& e, ConvT3& t, const View& dout, const View& in, Xf xf, const View& din) {
   hdf_plan* p = e.p;
-  const int* d = e.dm(t.lvl_in);
   // (the bias gradient comes out of the epilogue of the dgrad conv that produced dout: conv_backward)
-  WgradArgs w{};
-  w.sm = e.at(in);
-  w.sm_pitch = in.pitch;
-  w.SC = t.Cin;
-  w.lg = e.at(dout);
-  w.lg_pitch = dout.pitch;
-  w.LC = t.Cout;
-  w.N = e.B;
-  w.Ds = d[0], w.Hs = d[1], w.Ws = d[2];
-  w.Dl = (p->flat ? 1 : 2) * d[0], w.Hl = 2 * d[1], w.Wl = 2 * d[2];
-  w.sm_scale = xf.scale;
-  w.sm_shift = xf.shift;
-  w.sm_relu = xf.relu;
+  WgradArgs w = wgrad_args(e, in, t.Cin, dout, t.Cout);
+  w.sm_scale = xf.scale, w.sm_shift = xf.shift, w.sm_relu = xf.relu;
   HDF_TRY(hdf_launch_wgrad(p->dtype, 2, w, e.G(t.w), t.Cin, t.Cout, 0, e.ws + p->wgrad_ws, p->wgrad_ws_bytes,
                            e.wgrad_stream()));
   HDF_TRY(e.wgrad_done(dout));
   // dX[i][ci] = sum_k sum_co dY[2i-1+k][co] * W[ci][co][k]  -> stride-2 gather conv, packed [tap][CinP][Cout]
-  const int OP = round_up(t.Cin, 32);
-  ConvArgs a{};
-  a.in = e.at(dout);
-  a.in_pitch = dout.pitch;
-  a.Cin = t.Cout;
-  a.N = e.B;
-  a.Di = (p->flat ? 1 : 2) * d[0], a.Hi = 2 * d[1], a.Wi = 2 * d[2];
-  a.Do = d[0], a.Ho = d[1], a.Wo = d[2];
-  a.w = e.ws + t.wd;
-  a.wfrag = t.wd_frag;
-  a.out = e.at(din);
-  a.out_pitch = din.pitch;
-  a.Cout = t.Cin;
-  a.CoutP = OP;
-  return hdf_launch_conv(p->dtype, 1, a, e.st);
+  return hdf_launch_conv(p->dtype, 1, conv_args(e, dout, t.Cout, din, t.Cin, t.wd, t.wd_frag), e.st);
 }
 
-// fuse_in: the conv layer whose InstanceNorm+ReLU output the head reads -- the head gradient is then that activation's
-// complete gradient, and the kernel also writes the first pass of the layer's InstanceNorm backward (*pre_blocks rows
-// per sample in inb_partials; 0 when the table does not hold that many rows and the separate pass has to run)
-int head_backward(Exec& e, const Head1& h, const void* dlogits, const View& in, Xf xf, const View& dx, int acc,
-                  const Conv3* fuse_in = nullptr, int* pre_blocks = nullptr) {
+struct HeadBwd {
+  int accumulate = 0;               // 1: the input gradient is added to dx
+  // fuse_in: the conv layer whose InstanceNorm+ReLU output the head reads -- the head gradient is then that activation's
+  // complete gradient, and the kernel also writes the first pass of the layer's InstanceNorm backward (*pre_blocks rows
+  // per sample in inb_partials; 0 when the table does not hold that many rows and the separate pass has to run)
+  const Conv3* fuse_in = nullptr;
+  int* pre_blocks = nullptr;
+};
+int head_backward(Exec& e, const Head1& h, const void* dlogits, const View& in, Xf xf, const View& dx, const HeadBwd& o) {
   hdf_plan* p = e.p;
   const int hb = hdf_head_bwd_blocks(p->vox(h.lvl));
-  const bool fuse = fuse_in && pre_blocks && hb <= 1024;
-  if (pre_blocks) *pre_blocks = fuse ? hb : 0;
+  const bool fuse = o.fuse_in && o.pre_blocks && hb <= 1024;
+  if (o.pre_blocks) *o.pre_blocks = fuse ? hb : 0;
   return hdf_launch_head_bwd(p->dtype, dlogits, e.at(in), in.pitch, xf.scale, xf.shift, e.P(h.w), e.at(dx), dx.pitch,
-                             acc, e.G(h.w), e.G(h.b), e.B, h.C, p->ncls, p->vox(h.lvl), e.st,
-                             fuse ? e.f(fuse_in->st.mean) : nullptr, fuse ? e.f(fuse_in->st.rstd) : nullptr,
+                             o.accumulate, e.G(h.w), e.G(h.b), e.B, h.C, p->ncls, p->vox(h.lvl), e.st,
+                             fuse ? e.f(o.fuse_in->st.mean) : nullptr, fuse ? e.f(o.fuse_in->st.rstd) : nullptr,
                              fuse ? e.inbp() : nullptr);
 }
 
 }  // namespace
-
-// A persistent transformer launch that gave up (transformer_chain.hip: chain_wait) leaves 1 + a workgroup id in its timeout
-// word.  NaN written into the branch output does NOT survive the network -- relu(InstanceNorm(.)) is fmaxf(x * scale +
-// shift, 0), and fmaxf returns the operand that is not NaN -- so the step would end with finite, plausible-looking logits
-// and gradients.  These two launches (one workgroup each, the LAST launch of a forward / of a backward on the caller's
-// stream, only when the persistent kernels ran) make the failure visible in the data itself: the first rows of every output
-// / the head of the flat gradient buffer become NaN, so the loss, and the optimizer step, are NaN.
-template <typename T>
-__global__ void chain_poison_outputs_kernel(const unsigned* __restrict__ tmo, T* o0, T* o1, T* o2, T* o3, int n0, int n1,
-                                            int n2, int n3) {
-  if (__hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;
-  T* o[4] = {o0, o1, o2, o3};
-  const int n[4] = {n0, n1, n2, n3};
-  for (int k = 0; k < 4; k++)
-    for (int i = threadIdx.x; i < n[k]; i += blockDim.x) ST<T>::st(o[k] + i, __builtin_nanf(""));
-}
-__global__ void chain_poison_grads_kernel(const unsigned* __restrict__ tmo, float* grads, int n) {
-  if (__hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) grads[i] = __builtin_nanf("");
-}
 
 // Stand-in for a collective's kernel (tests / tools): `workgroups` workgroups of 256 threads that each hold `lds_bytes` of
 // LDS (160 KiB = a compute unit of its own) and `vgprs` vector registers per lane (0: a handful; 128: what a RCCL
@@ -813,7 +308,9 @@ static int upconv_chain_backward(Exec& e, int batch) {
     // input of up[k]: attnout (k==0) or at_{lvl} ; its gradient buffer already holds the skip-path gradient
     const View& cin = (k == 0) ? p->attnout : p->at[c.lvl];
     View din = (k == 0) ? p->dX4 : p->dSkip[c.lvl];
-    HDF_TRY(conv_backward(e, c, dy, cin, none, &din, 1));
+    ConvBwd o;
+    o.din = &din, o.accumulate = 1;
+    HDF_TRY(conv_backward(e, c, dy, cin, none, o));
   }
   {
     Conv3& c = p->deep;
@@ -821,7 +318,9 @@ static int upconv_chain_backward(Exec& e, int batch) {
     HDF_TRY(hdf_launch_upsample_bwd(p->dtype, e.at(p->dX4), p->dX4.pitch, e.at(p->dUa[0]), p->dUa[0].pitch, batch,
                                     c.Cout, d[0], d[1], d[2], e.st, p->flat ? 1 : 0));
     HDF_TRY(in_backward(e, c, p->dUa[0], p->dUy[0]));
-    HDF_TRY(conv_backward(e, c, p->dUy[0], p->attnall, none, &p->dAttnall, 0));
+    ConvBwd o;
+    o.din = &p->dAttnall;
+    HDF_TRY(conv_backward(e, c, p->dUy[0], p->attnall, none, o));
   }
   return HDF_OK;
 }
@@ -866,22 +365,20 @@ static int forward3d(hdf_plan* p, const float* x, const float* params, void* wor
                             hdf_conv_first_takes(p->dtype, p->enc[0][0].Cin, p->enc[0][0].Cout, p->dims[0][0], p->dims[0][1],
                                                  p->dims[0][2], p->xin.pitch);
   hipStream_t pst = first_direct ? bst : e.st;
-  if (first_direct) {
+  auto first_layer = [&]() -> int {
     HDF_TRY(hdf_launch_nchw_to_ndhwc(p->dtype, x, e.at(p->xin), batch, p->M, 16, p->vox(0), e.st));
-    HDF_TRY(conv_forward(e, p->enc[0][0], p->xin, none));
-  }
+    return conv_forward(e, p->enc[0][0], p->xin, none);
+  };
+  if (first_direct) HDF_TRY(first_layer());
   HDF_TRY(hdf_launch_pack_batch(p->dtype, params, e.ws, p->pack_jobs.data(), (int)p->pack_jobs.size(), pst));
   if (p->tf_fwd_chain)
-    HDF_TRY(tf_chain_pack(tf_dims(p, batch), tf_chain_params(p), p->nb, params, e.ws + p->tf_wpack, pst));
+    HDF_TRY(tf_chain_pack(tf_dims(p, batch), p->tf_cp, p->nb, params, e.ws + p->tf_wpack, pst));
   // (the caller's stream waits here only where the packs went to the branch stream; the branch stream waits below)
   hipEvent_t packed = bst ? e.order(pst, e.st, "the caller's stream behind the weight packs", first_direct) : nullptr;
   if (bst && !packed) return HDF_ERR_HIP;
   // the caller's stream first (4 launches), then the ~65 launches of the branch: the host issues launches one after the
   // other, and whatever is issued second starts that much later when the host is not far ahead of the GPU
-  if (!first_direct) {
-    HDF_TRY(hdf_launch_nchw_to_ndhwc(p->dtype, x, e.at(p->xin), batch, p->M, 16, p->vox(0), e.st));
-    HDF_TRY(conv_forward(e, p->enc[0][0], p->xin, none));
-  }
+  if (!first_direct) HDF_TRY(first_layer());
   // (round 5) The second level-0 conv takes three quarters of the compute units: it runs while the branch stream works
   // through deep_conv / up1..3 (the persistent transformer kernel in front of them holds every unit, so the order on
   // the device is conv_first, transformer, then this conv NEXT TO the UpConv chain), and the chain's low-resolution
@@ -968,21 +465,8 @@ static int forward3d(hdf_plan* p, const float* x, const float* params, void* wor
     dec_xf = xf_of(e, p->dec[k][1]);
     HDF_TRY(head_forward(e, p->head[k], *dec_in, dec_xf, outs[k]));
   }
-  if (p->tf_fwd_chain) {  // (see chain_poison_outputs_kernel: a launch that gave up must not leave plausible outputs)
-    const unsigned* tmo = reinterpret_cast<const unsigned*>(e.ws + p->tf_sync) + p->M * batch * 32;
-    int n[4];
-    for (int i = 0; i < 4; i++) n[i] = (int)std::min<int64_t>(p->vox(i) * p->ncls * batch, 4096);
-    if (p->dtype == HDF_F32)
-      hipLaunchKernelGGL(chain_poison_outputs_kernel<float>, dim3(1), dim3(256), 0, e.st, tmo, (float*)outs[0], (float*)outs[1],
-                         (float*)outs[2], (float*)outs[3], n[0], n[1], n[2], n[3]);
-    else if (p->dtype == HDF_BF16)
-      hipLaunchKernelGGL(chain_poison_outputs_kernel<bf16_t>, dim3(1), dim3(256), 0, e.st, tmo, (bf16_t*)outs[0],
-                         (bf16_t*)outs[1], (bf16_t*)outs[2], (bf16_t*)outs[3], n[0], n[1], n[2], n[3]);
-    else
-      hipLaunchKernelGGL(chain_poison_outputs_kernel<f16_t>, dim3(1), dim3(256), 0, e.st, tmo, (f16_t*)outs[0], (f16_t*)outs[1],
-                         (f16_t*)outs[2], (f16_t*)outs[3], n[0], n[1], n[2], n[3]);
-    HDF_LAUNCH_CHECK();
-  }
+  // (a persistent launch that gave up must not leave plausible outputs: exec_tf.hip, chain_poison_outputs_kernel)
+  if (p->tf_fwd_chain) HDF_TRY(chain_poison_outputs(e, outs));
   return HDF_OK;
 }
 
@@ -1056,17 +540,21 @@ static int backward3d(hdf_plan* p, const float* x, const float* params, void* wo
     Conv3 &c1 = p->dec[k][0], &c2 = p->dec[k][1];
     // gA[k] holds d/d(activation of c2): head gradient (+ convT input gradient from the level above, k>0)
     int pre = 0;
-    HDF_TRY(head_backward(e, p->head[k], douts[k], c2.y, xf_of(e, c2), p->gA[k], k > 0 ? 1 : 0, &c2, &pre));
+    HeadBwd ho;
+    ho.accumulate = k > 0 ? 1 : 0, ho.fuse_in = &c2, ho.pre_blocks = &pre;
+    HDF_TRY(head_backward(e, p->head[k], douts[k], c2.y, xf_of(e, c2), p->gA[k], ho));
     int bsr = 0;  // the data-gradient conv may leave the first pass of c1's InstanceNorm backward behind (level 0)
-    HDF_TRY(norm_conv_backward(e, c2, p->gA[k], p->gY[k], pre, c1.y, xf_of(e, c1), &p->gA[k], 0, nullptr, nullptr, 0, &c1,
-                               &bsr));
+    ConvBwd o2;
+    o2.pre_blocks = pre, o2.din = &p->gA[k], o2.bs_next = &c1, o2.bs_rows = &bsr;
+    HDF_TRY(norm_conv_backward(e, c2, p->gA[k], p->gY[k], c1.y, xf_of(e, c1), o2));
     // the upconv half of d(cat) is the gradient of upconv_{k+1}'s output: its bias gradient rides on this conv
-    float* up_db = e.G(p->upc[k].b);
+    ConvBwd o1;
+    o1.pre_blocks = bsr, o1.din_colsum = e.G(p->upc[k].b), o1.colsum_C = ch[k];
     if (p->dcat_split[k])
-      HDF_TRY(norm_conv_backward(e, c1, p->gA[k], p->gY2[k], bsr, p->cat[k], none, &p->dUp[k], 0, &p->dSkip[k], up_db,
-                                 ch[k]));
+      o1.din = &p->dUp[k], o1.din2 = &p->dSkip[k];
     else
-      HDF_TRY(norm_conv_backward(e, c1, p->gA[k], p->gY2[k], bsr, p->cat[k], none, &p->dCat[k], 0, nullptr, up_db, ch[k]));
+      o1.din = &p->dCat[k];
+    HDF_TRY(norm_conv_backward(e, c1, p->gA[k], p->gY2[k], p->cat[k], none, o1));
     // upconv_{k+1}: input is dec[k+1][1] activation (k<2) or the bottleneck x4 (k==2)
     const View& dup = p->dUp[k];
     if (k < 2)
@@ -1074,7 +562,9 @@ static int backward3d(hdf_plan* p, const float* x, const float* params, void* wo
     else
       HDF_TRY(convt_backward(e, p->upc[k], dup, p->x4, none, p->dX4));
   }
-  HDF_TRY(head_backward(e, p->head[3], douts[3], p->x4, none, p->dX4, 1));
+  HeadBwd h3;
+  h3.accumulate = 1;
+  HDF_TRY(head_backward(e, p->head[3], douts[3], p->x4, none, p->dX4, h3));
   HDF_TRY(record_joined(BK_DEC, e));   // upconv_1..3, block_*_right, the four heads: nothing below touches their gradients
 
   // ---- encoder, bottom (level 3) up to level 0.  dskip: gradient of ds_k (= of the transformer feature at_k too)
@@ -1118,8 +608,9 @@ static int backward3d(hdf_plan* p, const float* x, const float* params, void* wo
       }
     }
     int bsr = 0;
-    HDF_TRY(norm_conv_backward(e, c2, dskip, p->gY[k], pre, c1.y, xf_of(e, c1), &p->gA[k], 0, nullptr, nullptr, 0, &c1,
-                               &bsr));
+    ConvBwd o2;
+    o2.pre_blocks = pre, o2.din = &p->gA[k], o2.bs_next = &c1, o2.bs_rows = &bsr;
+    HDF_TRY(norm_conv_backward(e, c2, dskip, p->gY[k], c1.y, xf_of(e, c1), o2));
     bool first_fused = false;
     // The first layer has no input gradient: the second pass of its InstanceNorm backward would write dy (268 MB at the
     // benchmark size) only for the weight gradient to read it back.  wgrad_first_kernel applies that pass to the rows it
@@ -1127,7 +618,9 @@ static int backward3d(hdf_plan* p, const float* x, const float* params, void* wo
     if (k == 0 && hdf_wgrad_first_takes(p->dtype, c1.Cin, c1.Cout, p->dims[0][0], p->dims[0][1], p->dims[0][2],
                                         p->xin.pitch, p->gA[k].pitch)) {
       float* kk = e.f(p->inb_k3);
-      HDF_TRY(in_backward(e, c1, p->gA[k], p->gY2[k], bsr, false, kk));
+      InBwd ib;
+      ib.pre_blocks = bsr, ib.apply = false, ib.kbuf = kk;
+      HDF_TRY(in_backward(e, c1, p->gA[k], p->gY2[k], ib));
       const WgradFirstIn fi{e.at(c1.y), c1.y.pitch, e.f(c1.st.scale), e.f(c1.st.shift), e.f(c1.st.mean), e.f(c1.st.rstd),
                             kk, kk + (size_t)e.B * c1.Cout, kk + (size_t)2 * e.B * c1.Cout};
       HDF_TRY(hdf_launch_wgrad_first(p->dtype, e.at(p->gA[k]), p->gA[k].pitch, c1.Cout, e.at(p->xin), p->xin.pitch, c1.Cin,
@@ -1137,10 +630,9 @@ static int backward3d(hdf_plan* p, const float* x, const float* params, void* wo
       first_fused = true;
     }
     if (!first_fused) {
-      if (k > 0)
-        HDF_TRY(norm_conv_backward(e, c1, p->gA[k], p->gY2[k], bsr, p->pooled[k - 1], none, &p->dP[k - 1], 0));
-      else
-        HDF_TRY(norm_conv_backward(e, c1, p->gA[k], p->gY2[k], bsr, p->xin, none, nullptr, 0));
+      ConvBwd o1;  // (the first layer has no input gradient)
+      o1.pre_blocks = bsr, o1.din = k > 0 ? &p->dP[k - 1] : nullptr;
+      HDF_TRY(norm_conv_backward(e, c1, p->gA[k], p->gY2[k], k > 0 ? p->pooled[k - 1] : p->xin, none, o1));
     }
     if (k == 1) HDF_TRY(record_joined(BK_ENC, e));   // block_2_* .. block_4_*_left: the encoder below the top level is done
     // (host order: the ten level-0 launches of the caller's stream first, then the ~100 of the transformer backward)
@@ -1174,12 +666,7 @@ static int backward3d(hdf_plan* p, const float* x, const float* params, void* wo
     }
   }
   e.join();
-  if ((stages & 4) && p->tf_bwd_chain) {  // (chain_poison_grads_kernel: the persistent backward's timeout word, second half)
-    const unsigned* tmo = reinterpret_cast<const unsigned*>(e.ws + p->tf_sync) + (1 << 17) + p->M * batch * 32;
-    hipLaunchKernelGGL(chain_poison_grads_kernel, dim3(1), dim3(256), 0, e.st, tmo, grads,
-                       (int)std::min<int64_t>(p->total_floats, 4096));
-    HDF_LAUNCH_CHECK();
-  }
+  if ((stages & 4) && p->tf_bwd_chain) HDF_TRY(chain_poison_grads(e));
   return HDF_OK;
 }
 
@@ -1285,27 +772,6 @@ int hdf_backward_events(hdf_plan* p, const float* x, const float* params, void* 
   }
   return backward_any(p, x, params, workspace, workspace_bytes, dout0, dout1, dout2, dout3, grads, batch, 7, stream,
                       p->bucket_ev);
-}
-
-int hdf_plan_set_chain_timeout_us(hdf_plan* p, int64_t usec) {
-  HDF_CHECK_ARG(p && usec >= 100 && usec <= 30000000, "plan_set_chain_timeout_us: 100 us .. 30 s");
-  p->chain_ticks = (unsigned)(usec * 100);   // s_memrealtime: 100 MHz
-  return HDF_OK;
-}
-
-int hdf_plan_force_persistent(hdf_plan* p, int on) {
-  HDF_CHECK_ARG(p != nullptr, "plan_force_persistent: null plan");
-  p->chain_forced = on != 0;
-  return HDF_OK;
-}
-
-int hdf_plan_chain_state(hdf_plan* p, int batch, int* persistent, int* gave_up_workgroup) {
-  HDF_CHECK_ARG(p && batch >= 1, "plan_chain_state: null plan / batch < 1");
-  // (reads the host-mapped word like the next forward would, without consuming it: that call still reports the error)
-  const unsigned pending = p->chain_flag ? __atomic_load_n(p->chain_flag, __ATOMIC_ACQUIRE) : 0u;
-  if (gave_up_workgroup) *gave_up_workgroup = pending ? (int)pending - 1 : (p->chain_last_giveup ? (int)p->chain_last_giveup - 1 : -1);
-  if (persistent) *persistent = (!pending && tf_use_chain(p, batch)) ? 1 : 0;
-  return HDF_OK;
 }
 
 int hdf_op_occupy(int workgroups, int lds_bytes, int vgprs, int usec, hdf_stream stream) {

@@ -1,11 +1,10 @@
 // Model plan: owns the parameter table (= the reference state_dict, HDenseFormer.py:178-227), the layer table and
-// the workspace layout.  Host arithmetic only -- no kernel, no launch (the launch sequences over a plan: exec.hip);
-// every device buffer is caller-owned.
+// the workspace layout.  Host arithmetic only -- no kernel, no launch (the launch sequences over a plan: exec.hip,
+// exec_tf.hip); every device buffer is caller-owned.
 #include <cstdarg>
 #include <cstring>
 
 #include "plan_internal.h"
-#include "transformer.h"
 
 namespace {
 
@@ -101,6 +100,50 @@ void build_params(hdf_plan* p) {
   head("conv1x1_d1", 2 * nf);
   head("conv1x1_d2", 4 * nf);
   head("conv1x1_d3", 8 * nf);
+}
+
+// Transformer addressing of modality 0 (hdf_plan::tf_cp / tf_wg / pe_*; modality m: + m * mstride).  The executor reaches
+// tensor k of layer l of block b as blk0 + b * blk_stride + loff[l][k]: checked here, from the names, for every block.
+int build_tf_tables(hdf_plan* p) {
+  static const char* const LAYER[13] = {"0.weight", "0.bias", "1.norm.weight", "1.norm.bias", "1.fn.to_qkv.weight",
+                                        "1.fn.to_out.0.weight", "1.fn.to_out.0.bias", "2.norm.weight", "2.norm.bias",
+                                        "2.fn.net.0.weight", "2.fn.net.0.bias", "2.fn.net.3.weight", "2.fn.net.3.bias"};
+  static const char* const OUT[4] = {"0.weight", "0.bias", "3.weight", "3.bias"};  // (the member order of TfLayerP / TfOutP)
+  auto layer = [&](int b, int l, int k) {
+    return p->P("attns.0.blocks." + std::to_string(b) + ".0.layers." + std::to_string(l) + "." + LAYER[k]);
+  };
+  auto out = [&](int b, int k) { return p->P("attns.0.blocks." + std::to_string(b) + ".0.out_layer.net." + OUT[k]); };
+  TfChainP& c = p->tf_cp;
+  c.blk0 = layer(0, 0, 0);
+  c.blk_stride = p->nb > 1 ? layer(1, 0, 0) - c.blk0 : 0;
+  for (int l = 0; l < 4; l++)
+    for (int k = 0; k < 13; k++) c.loff[l][k] = (int32_t)(layer(0, l, k) - c.blk0);
+  for (int k = 0; k < 4; k++) c.ooff[k] = (int32_t)(out(0, k) - c.blk0);
+  for (int b = 0; b < p->nb; b++) {
+    const int64_t blk = c.blk0 + b * c.blk_stride;
+    bool ok = true;
+    for (int l = 0; l < 4; l++)
+      for (int k = 0; k < 13; k++) ok = ok && layer(b, l, k) >= 0 && layer(b, l, k) == blk + c.loff[l][k];
+    for (int k = 0; k < 4; k++) ok = ok && out(b, k) >= 0 && out(b, k) == blk + c.ooff[k];
+    HDF_CHECK_ARG(ok, "plan_create: transformer block %d is not laid out like block 0 at %lld + %d * %lld floats", b,
+                  (long long)c.blk0, b, (long long)c.blk_stride);
+  }
+  const int DM = p->DM, DMF = p->DMF;
+  TfWgradEntry* e = p->tf_wg;
+  for (int l = 0; l < 4; l++) {
+    const int32_t* o = c.loff[l];
+    *e++ = TfWgradEntry{o[4], 96, 32, l, 0, 0, TF_T_DQ, TF_T_T, -1, -1, 96, 32};                                // to_qkv
+    *e++ = TfWgradEntry{o[0], 32, DM + 32 * l, l, 0, 1, TF_T_DH0, 0, -1, -1, 32, DMF};                          // Linear0
+    *e++ = TfWgradEntry{o[11], 32, 64, l, 0, 0, TF_T_P1, TF_T_P1 + 32, TF_T_P0, TF_T_P0 + 32, 32, 64};          // net.3
+    *e++ = TfWgradEntry{o[9], 64, 32, l, 0, 0, TF_T_P1 + 96, TF_T_P1 + 160, TF_T_P0 + 96, TF_T_P0 + 160, 64, 32};  // net.0
+    *e++ = TfWgradEntry{o[5], 32, 32, l, 0, 2, TF_T_DGO, 0, -1, -1, 32, 32};                                    // to_out
+  }
+  *e++ = TfWgradEntry{c.ooff[2], DM, 64, 0, 3, 3, 0, DM, -1, -1, DM, 64};          // out_layer.net.3
+  *e++ = TfWgradEntry{c.ooff[0], 64, DMF, 0, 3, 1, DM + 64, 0, -1, -1, 64, DMF};   // out_layer.net.0
+  p->pe_w = p->P("attns.0.patch_embeddings.weight");
+  p->pe_b = p->P("attns.0.patch_embeddings.bias");
+  p->pe_pos = p->P("attns.0.position_embeddings");
+  return HDF_OK;
 }
 
 void init_conv(hdf_plan* p, Conv3& c, const std::string& name, int cin, int cout, int lvl, bool basic) {
@@ -406,14 +449,13 @@ static int create_plan(int in_channels, int n_cls, int n_filters, int D, int H, 
   p->DMF = p->DM + 128;
   p->Ntok = (D / 16) * (H / 16) * (W / 16);
   build_params(p);
+  int rc = build_tf_tables(p);
   build_layers(p);
   p->is2d = is2d;
-  if (is2d) {
-    int rc = build_params2d(p);
-    if (rc != HDF_OK) {
-      delete p;
-      return rc;
-    }
+  if (rc == HDF_OK && is2d) rc = build_params2d(p);
+  if (rc != HDF_OK) {
+    delete p;
+    return rc;
   }
   *out = p;
   return HDF_OK;

@@ -1,7 +1,9 @@
 // The plan's types and the few functions its units call across each other (private to csrc/: not installed).
 //   plan.hip     parameter table, layer table, workspace carving, the hdf_plan_* queries (host arithmetic only)
 //   embed2d.hip  the 2-D embedding's kernels and launchers
-//   exec.hip     Exec (streams, event ring) and the forward / backward launch sequences
+//   exec.hip     the U-Net layer helpers, the forward / backward launch sequences, the rest of the C ABI
+//   exec_tf.hip  the transformer branches' launch sequences and the persistent kernels' give-up handling
+//   (exec_internal.h: what those two share -- Exec (streams, event ring), Rejoin, Xf)
 #pragma once
 #include <map>
 #include <string>
@@ -9,6 +11,7 @@
 
 #include "../../include/hdf.h"
 #include "conv_igemm.h"
+#include "transformer.h"
 
 // (a named namespace: the inline members and container instantiations of these types are weak symbols in the shared
 // library's dynamic table, where a bare `View` invites a collision)
@@ -85,6 +88,11 @@ struct hdf_plan {
   std::map<std::string, int64_t> pidx;
   int64_t total_floats = 0;
   int64_t mstride = 0;
+  // Transformer parameter addressing, resolved from the names once at creation (plan.hip: build_tf_tables, which also checks
+  // that every block is spaced as tf_cp says): the persistent kernels' offsets, tf_wgrad's matrices, the patch embedding
+  TfChainP tf_cp{};
+  TfWgradEntry tf_wg[TF_WG_ENTRIES];
+  int64_t pe_w = -1, pe_b = -1, pe_pos = -1;
   // layers
   Conv3 deep, up[3], enc[4][2], dec[3][2];  // dec[k]: level k (0..2) right blocks
   ConvT3 upc[3];                            // upc[k] produces level k from level k+1

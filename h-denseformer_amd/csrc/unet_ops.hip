@@ -1171,54 +1171,6 @@ __global__ __launch_bounds__(256) void in_bwd_apply_kernel(const T* __restrict__
   }
 }
 
-template <typename T>
-__global__ void add_kernel(T* __restrict__ a, int64_t a_pitch, const T* __restrict__ b, int64_t b_pitch, int C,
-                           int64_t rows, int accumulate) {
-  constexpr int EPC = ST<T>::EPC;
-  const int cols = C / EPC;
-  int64_t total = rows * cols;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t row = i / cols;
-    int c0 = (int)(i - row * cols) * EPC;
-    float f[EPC], g[EPC];
-    load_chunk<T>(b + row * b_pitch + c0, g);
-    if (accumulate) {
-      load_chunk<T>(a + row * a_pitch + c0, f);
-#pragma unroll
-      for (int e = 0; e < EPC; e++) g[e] += f[e];
-    }
-    store_chunk<T>(a + row * a_pitch + c0, g);
-  }
-}
-
-// db[c] += sum over rows; block partial in LDS then one atomic per channel per block
-template <typename T>
-__global__ __launch_bounds__(256) void bias_grad_kernel(const T* __restrict__ dy, int64_t dy_pitch,
-                                                        float* __restrict__ db, int C, int64_t rows) {
-  constexpr int EPC = ST<T>::EPC;
-  extern __shared__ float red[];  // [C]
-  const int cols = C / EPC;
-  const int vlanes = 256 / cols;
-  const int col = threadIdx.x % cols, vl = threadIdx.x / cols;
-  for (int i = threadIdx.x; i < C; i += 256) red[i] = 0.f;
-  __syncthreads();
-  float s[EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; e++) s[e] = 0.f;
-  if (vl < vlanes) {
-    for (int64_t r = (int64_t)blockIdx.x * vlanes + vl; r < rows; r += (int64_t)gridDim.x * vlanes) {
-      float f[EPC];
-      load_chunk<T>(dy + r * dy_pitch + col * EPC, f);
-#pragma unroll
-      for (int e = 0; e < EPC; e++) s[e] += f[e];
-    }
-#pragma unroll
-    for (int e = 0; e < EPC; e++) atomicAdd(&red[col * EPC + e], s[e]);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < C; i += 256) atomicAdd(db + i, red[i]);
-}
-
 inline unsigned grid_for(int64_t total, int block = 256) {
   return (unsigned)std::min<int64_t>(ceil_div64(total, block), MAX_BLOCKS);
 }
@@ -1236,11 +1188,9 @@ static int allow_big_lds(const void* kern, size_t bytes) {
   return HDF_OK;
 }
 
-#define DISPATCH_T HDF_DISPATCH_T
-
 int hdf_launch_nchw_to_ndhwc(int dtype, const float* x, void* out, int N, int C, int CP, int64_t vox, hipStream_t st) {
   HDF_CHECK_ARG(CP % 16 == 0 && CP >= C, "nchw_to_ndhwc: CP=%d", CP);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(nchw_to_ndhwc_kernel<T>, dim3(grid_for((int64_t)N * vox)), dim3(256), 0, st, x,
+  HDF_DISPATCH_T(dtype, hipLaunchKernelGGL(nchw_to_ndhwc_kernel<T>, dim3(grid_for((int64_t)N * vox)), dim3(256), 0, st, x,
                                        (T*)out, N, C, CP, vox));
   HDF_LAUNCH_CHECK();
   return HDF_OK;
@@ -1290,7 +1240,7 @@ int hdf_launch_norm_relu_add(int dtype, const void* y, int64_t y_pitch, const fl
                              const void* skip, int64_t skip_pitch, void* out, int64_t out_pitch, int N, int C,
                              int64_t vox, hipStream_t st) {
   HDF_CHECK_ARG(C % 16 == 0, "norm_relu_add: C=%d", C);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(norm_relu_add_kernel<T>, dim3(grid_for((int64_t)N * vox * (C / ST<T>::EPC))),
+  HDF_DISPATCH_T(dtype, hipLaunchKernelGGL(norm_relu_add_kernel<T>, dim3(grid_for((int64_t)N * vox * (C / ST<T>::EPC))),
                                        dim3(256), 0, st, (const T*)y, y_pitch, scale, shift, (const T*)skip, skip_pitch,
                                        (T*)out, out_pitch, N, C, vox));
   HDF_LAUNCH_CHECK();
@@ -1305,14 +1255,11 @@ int hdf_launch_enc_tail(int dtype, const void* y, int64_t y_pitch, const float* 
   // (a form with the two x neighbours of a pooled voxel on neighbouring lanes -- whole contiguous rows per instruction, the
   // partial maxima merged through one lane exchange -- was built and measured: 163 vs 155 us at 128^3; this form already
   // streams at 5.5 TB/s alone, the 206 us it shows inside a step come from what runs around it)
-  DISPATCH_T(dtype, {
+  HDF_DISPATCH_T(dtype, {
     unsigned g = grid_for((int64_t)N * Do * Ho * Wo * (C / ST<T>::EPC));
-    if (flat)
-      hipLaunchKernelGGL((enc_tail_kernel<T, true>), dim3(g), dim3(256), 0, st, (const T*)y, y_pitch, scale, shift,
-                         (const T*)skip, skip_pitch, (T*)ds, ds_pitch, (T*)pooled, pooled_pitch, idx, N, C, Do, Ho, Wo);
-    else
-      hipLaunchKernelGGL((enc_tail_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)y, y_pitch, scale, shift,
-                         (const T*)skip, skip_pitch, (T*)ds, ds_pitch, (T*)pooled, pooled_pitch, idx, N, C, Do, Ho, Wo);
+    auto kern = flat ? enc_tail_kernel<T, true> : enc_tail_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, st, (const T*)y, y_pitch, scale, shift, (const T*)skip, skip_pitch,
+                       (T*)ds, ds_pitch, (T*)pooled, pooled_pitch, idx, N, C, Do, Ho, Wo);
   });
   HDF_LAUNCH_CHECK();
   return HDF_OK;
@@ -1323,7 +1270,7 @@ int hdf_launch_enc_tail_up(int dtype, const void* y, int64_t y_pitch, const floa
                            int64_t ds_pitch, void* pooled, int64_t pooled_pitch, uint8_t* idx, int N, int C, int Do, int Ho,
                            int Wo, hipStream_t st) {
   HDF_CHECK_ARG(C % 16 == 0, "enc_tail_up: C=%d", C);
-  DISPATCH_T(dtype, {
+  HDF_DISPATCH_T(dtype, {
     HDF_CHECK_ARG(Ho <= 65535 && (int64_t)N * Do <= 65535, "enc_tail_up: extent %d x %d x %d", Do, Ho, Wo);
     hipLaunchKernelGGL((enc_tail_up_kernel<T>), dim3(ceil_div(Wo * (C / 4), 256), Ho, N * Do), dim3(256), 0, st, (const T*)y, y_pitch, scale, shift,
                        (const T*)low, low_pitch, lscale, lshift, (T*)ds, ds_pitch, (T*)pooled, pooled_pitch, idx, N, C, Do,
@@ -1336,7 +1283,7 @@ int hdf_launch_enc_tail_up(int dtype, const void* y, int64_t y_pitch, const floa
 int hdf_launch_maxpool_fwd(int dtype, const void* in, int64_t in_pitch, void* out, int64_t out_pitch, uint8_t* idx,
                            int N, int C, int Do, int Ho, int Wo, hipStream_t st) {
   HDF_CHECK_ARG(C % 16 == 0, "maxpool: C=%d", C);
-  DISPATCH_T(dtype,
+  HDF_DISPATCH_T(dtype,
              hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(grid_for((int64_t)N * Do * Ho * Wo * (C / ST<T>::EPC))),
                                 dim3(256), 0, st, (const T*)in, in_pitch, (T*)out, out_pitch, idx, N, C, Do, Ho, Wo));
   HDF_LAUNCH_CHECK();
@@ -1440,22 +1387,19 @@ int hdf_launch_maxpool_bwd_in(int dtype, const void* dout, int64_t dout_pitch, c
   HDF_CHECK_ARG((int64_t)Do * Ho * Wo < ((int64_t)1 << 28), "maxpool_bwd_in: %dx%dx%d pooled voxels per sample", Do, Ho, Wo);
   const int blocks = hdf_maxpool_bwd_in_blocks((int64_t)Do * Ho * Wo, C);
   const int vlanes = 256 / (C / 4);
-  if (flat) {
-    DISPATCH_T(dtype, hipLaunchKernelGGL((maxpool_bwd_inb_kernel<T, true>), dim3(blocks, N), dim3(256),
-                                         (size_t)vlanes * C * 2 * sizeof(float), st, (const T*)dout, dout_pitch, idx, (T*)din,
-                                         din_pitch, (const T*)y, y_pitch, scale, shift, mean, rstd, partials, C, Do, Ho, Wo));
-  } else {
-    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_bwd_inb_kernel<T>, dim3(blocks, N), dim3(256),
-                                         (size_t)vlanes * C * 2 * sizeof(float), st, (const T*)dout, dout_pitch, idx, (T*)din,
-                                         din_pitch, (const T*)y, y_pitch, scale, shift, mean, rstd, partials, C, Do, Ho, Wo));
-  }
+  HDF_DISPATCH_T(dtype, {
+    auto kern = flat ? maxpool_bwd_inb_kernel<T, true> : maxpool_bwd_inb_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3(blocks, N), dim3(256), (size_t)vlanes * C * 2 * sizeof(float), st, (const T*)dout,
+                       dout_pitch, idx, (T*)din, din_pitch, (const T*)y, y_pitch, scale, shift, mean, rstd, partials, C, Do,
+                       Ho, Wo);
+  });
   HDF_LAUNCH_CHECK();
   return HDF_OK;
 }
 
 int hdf_launch_maxpool_bwd(int dtype, const void* dout, int64_t dout_pitch, const uint8_t* idx, void* din,
                            int64_t din_pitch, int N, int C, int Do, int Ho, int Wo, int accumulate, hipStream_t st) {
-  DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_bwd_kernel<T>,
+  HDF_DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_bwd_kernel<T>,
                                        dim3(grid_for((int64_t)N * Do * Ho * Wo * (C / ST<T>::EPC))), dim3(256), 0, st,
                                        (const T*)dout, dout_pitch, idx, (T*)din, din_pitch, N, C, Do, Ho, Wo,
                                        accumulate));
@@ -1468,15 +1412,11 @@ int hdf_launch_upsample_fwd(int dtype, const void* y, int64_t y_pitch, const flo
   HDF_CHECK_ARG(C % 16 == 0, "upsample: C=%d", C);
   HDF_CHECK_ARG(scale && shift, "upsample_fwd: the producer's InstanceNorm scale / shift are required");
   HDF_CHECK_ARG(!flat || Di == 1, "upsample_fwd: the 2-D form takes depth-1 tensors");
-  if (flat) {
-    DISPATCH_T(dtype, hipLaunchKernelGGL((upsample_fwd_kernel<T, true>),
-                                         dim3(grid_for((int64_t)N * Di * Hi * Wi * (C / ST<T>::EPC))), dim3(256), 0, st,
-                                         (const T*)y, y_pitch, scale, shift, (T*)out, out_pitch, N, C, Di, Hi, Wi));
-  } else {
-    DISPATCH_T(dtype, hipLaunchKernelGGL(upsample_fwd_kernel<T>,
-                                         dim3(grid_for((int64_t)N * Di * Hi * Wi * (C / ST<T>::EPC))), dim3(256), 0, st,
-                                         (const T*)y, y_pitch, scale, shift, (T*)out, out_pitch, N, C, Di, Hi, Wi));
-  }
+  HDF_DISPATCH_T(dtype, {
+    auto kern = flat ? upsample_fwd_kernel<T, true> : upsample_fwd_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3(grid_for((int64_t)N * Di * Hi * Wi * (C / ST<T>::EPC))), dim3(256), 0, st, (const T*)y,
+                       y_pitch, scale, shift, (T*)out, out_pitch, N, C, Di, Hi, Wi);
+  });
   HDF_LAUNCH_CHECK();
   return HDF_OK;
 }
@@ -1487,16 +1427,13 @@ int hdf_launch_upsample_bwd(int dtype, const void* dout, int64_t dout_pitch, voi
   HDF_CHECK_ARG((int64_t)8 * Di * Hi * Wi * dout_pitch < ((int64_t)1 << 31),
                 "upsample_bwd: a sample of %dx%dx%d voxels x pitch %lld exceeds 32-bit element offsets", 2 * Di, 2 * Hi,
                 2 * Wi, (long long)dout_pitch);
-  DISPATCH_T(dtype, {
+  HDF_DISPATCH_T(dtype, {
     const int gx = ceil_div(Wi * (C / ST<T>::EPC), 256);
     const int64_t wgs = (int64_t)gx * Hi * N * Di;
     HDF_CHECK_ARG(wgs < ((int64_t)1 << 31), "upsample_bwd: %lld workgroups", (long long)wgs);
-    if (flat)
-      hipLaunchKernelGGL((upsample_bwd_kernel<T, true>), dim3((unsigned)wgs), dim3(256), 0, st, (const T*)dout, dout_pitch,
-                         (T*)din, din_pitch, N, C, Di, Hi, Wi, gx);
-    else
-      hipLaunchKernelGGL(upsample_bwd_kernel<T>, dim3((unsigned)wgs), dim3(256), 0, st, (const T*)dout, dout_pitch, (T*)din,
-                         din_pitch, N, C, Di, Hi, Wi, gx);
+    auto kern = flat ? upsample_bwd_kernel<T, true> : upsample_bwd_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256), 0, st, (const T*)dout, dout_pitch, (T*)din, din_pitch, N, C, Di,
+                       Hi, Wi, gx);
   });
   HDF_LAUNCH_CHECK();
   return HDF_OK;
@@ -1512,7 +1449,7 @@ int hdf_launch_head_fwd(int dtype, const void* in, int64_t in_pitch, const float
   const int per = head_vox(vox, 1024) >= 256 ? head_vox(vox, 1024) : head_vox(vox);
   const unsigned gx = (unsigned)ceil_div64(vox, per);
   const int vec4 = (vox % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0) ? 1 : 0;
-  DISPATCH_T(dtype, {
+  HDF_DISPATCH_T(dtype, {
     // 8 class slots at per = 2048 (the 128^3 level) need 72 KiB of dynamic LDS: above 64 KiB it is allowed per kernel
     auto go = [&](auto kern, int mc) -> int {
       const size_t shm = (size_t)mc * (per + 256) * sizeof(float);
@@ -1544,7 +1481,7 @@ int hdf_launch_head_bwd(int dtype, const void* dlogits, const void* in, int64_t 
   const unsigned gx = (unsigned)hdf_head_bwd_blocks(vox);
   // logit-gradient planes by 4-voxel loads: whole aligned groups (per is a multiple of 64)
   const int vec4 = (vox % 4 == 0 && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0) ? 1 : 0;
-  DISPATCH_T(dtype, {
+  HDF_DISPATCH_T(dtype, {
     const int cols = C / 4, vlanes = 256 / cols;
     const int mc = ncls <= 4 ? 4 : 8;
     const size_t shm =
@@ -1574,7 +1511,7 @@ int hdf_launch_in_bwd_reduce(int dtype, const void* da, int64_t da_pitch, const 
                              const float* scale, const float* shift, const float* mean, const float* rstd,
                              float* partials, int blocks, int N, int C, int64_t vox, hipStream_t st) {
   HDF_CHECK_ARG(C % 16 == 0 && C <= 1024, "in_bwd: C=%d", C);
-  DISPATCH_T(dtype, {
+  HDF_DISPATCH_T(dtype, {
 #ifndef INB_HEAVY
     if constexpr (sizeof(T) == 2) {  // register-light form: co-runs with the side stream's weight gradients
       const int vlanes = 256 / (C / 4);
@@ -1611,7 +1548,7 @@ int hdf_launch_in_bwd_apply(int dtype, const void* da, int64_t da_pitch, const v
   HDF_CHECK_ARG(C % 16 == 0 && C <= 1024, "in_bwd_apply: C=%d", C);
   // ~1K chunks per workgroup, at most 2048 workgroups per sample
   const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, vox * (C / 8) / 1024));
-  DISPATCH_T(dtype, {
+  HDF_DISPATCH_T(dtype, {
 #ifndef INB_HEAVY
     if constexpr (sizeof(T) == 2)
       hipLaunchKernelGGL(in_bwd_apply4_kernel<T>, dim3(blocks, N), dim3(256), 0, st, (const T*)da, da_pitch, (const T*)y,
@@ -1620,28 +1557,6 @@ int hdf_launch_in_bwd_apply(int dtype, const void* da, int64_t da_pitch, const v
 #endif
       hipLaunchKernelGGL(in_bwd_apply_kernel<T>, dim3(blocks, N), dim3(256), 0, st, (const T*)da, da_pitch, (const T*)y,
                          y_pitch, scale, shift, mean, rstd, k1, ka, kb, (T*)dy, dy_pitch, C, vox);
-  });
-  HDF_LAUNCH_CHECK();
-  return HDF_OK;
-}
-
-int hdf_launch_add(int dtype, void* a, int64_t a_pitch, const void* b, int64_t b_pitch, int N, int C, int64_t vox,
-                   int accumulate, hipStream_t st) {
-  DISPATCH_T(dtype, hipLaunchKernelGGL(add_kernel<T>, dim3(grid_for((int64_t)N * vox * (C / ST<T>::EPC))), dim3(256), 0,
-                                       st, (T*)a, a_pitch, (const T*)b, b_pitch, C, (int64_t)N * vox, accumulate));
-  HDF_LAUNCH_CHECK();
-  return HDF_OK;
-}
-
-int hdf_launch_bias_grad(int dtype, const void* dy, int64_t dy_pitch, float* db, int C, int64_t nvox, hipStream_t st) {
-  HDF_CHECK_ARG(C % 16 == 0 && C <= 1024, "bias_grad: C=%d", C);
-  DISPATCH_T(dtype, {
-    int cols = C / ST<T>::EPC;
-    HDF_CHECK_ARG(cols <= 256, "bias_grad: C=%d too wide", C);
-    int vlanes = 256 / cols;
-    unsigned g = (unsigned)std::min<int64_t>(ceil_div64(nvox, (int64_t)vlanes * 8), 512);
-    hipLaunchKernelGGL(bias_grad_kernel<T>, dim3(g), dim3(256), C * sizeof(float), st, (const T*)dy, dy_pitch, db, C,
-                       nvox);
   });
   HDF_LAUNCH_CHECK();
   return HDF_OK;

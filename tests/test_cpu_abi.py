@@ -57,6 +57,20 @@ def test_plan_param_table_matches_reference_state_dict(lib, cfg):
     for m in range(1, cfg[0]):
         assert (o0[f"attns.{m}.position_embeddings"] - o0[f"attns.{m-1}.position_embeddings"]
                 == o0["attns.1.position_embeddings"] - o0["attns.0.position_embeddings"])
+    # every transformer block is laid out like block 0 (the plan resolves the 56 layer / out_layer tensors of a block once,
+    # as offsets from the block's first tensor, and reaches block b of branch m as blk0 + b * stride + m * mstride)
+    mstride = o0["attns.1.position_embeddings"] - o0["attns.0.position_embeddings"]
+    def block(m, b):
+        pre = f"attns.{m}.blocks.{b}.0."
+        return [(n[len(pre):], o) for n, o in o0.items() if n.startswith(pre)]
+    blk0 = block(0, 0)[0][1]
+    rel = [(n, o - blk0) for n, o in block(0, 0)]
+    nb = cfg[4] // 4
+    assert len(rel) == 4 * 13 + 4 and rel[0][0] == "layers.0.0.weight"
+    stride = block(0, 1)[0][1] - blk0 if nb > 1 else 0
+    for m in range(cfg[0]):
+        for b in range(nb):
+            assert block(m, b) == [(n, blk0 + b * stride + m * mstride + r) for n, r in rel], (m, b)
     assert plan.workspace_bytes(2) > 0
 
 

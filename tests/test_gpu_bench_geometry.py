@@ -397,7 +397,7 @@ def test_baseline_config_shapes_forward_vs_oracle_and_low_precision_step(name, c
 
 def test_weight_gradients_on_the_side_stream_are_reproducible():
     """The conv / transposed-conv weight gradients run on the plan's side stream next to the rest of backward
-    (csrc/exec.hip Exec).  They are summed in a fixed order, so the same step run three times must give bitwise equal
+    (csrc/exec_internal.h Exec).  They are summed in a fixed order, so the same step run three times must give bitwise equal
     gradients for every conv weight: a weight gradient that reads a dy buffer the main stream has already overwritten, or
     a join that comes too early, shows up as a difference.  (Biases, LayerNorm parameters and the heads use float
     atomics and are compared with a tolerance.)  bf16 storage at 64^3 x 2: every kernel family of the benchmark."""

@@ -115,7 +115,7 @@ def test_conv3d_weights_in_registers_accumulate_and_pitch(cin, cout, size, n):
 @pytest.mark.parametrize("cin,cout,size,n", [(32, 32, (8, 8, 16), 2), (32, 64, (48, 48, 52), 3), (64, 32, (52, 48, 48), 1),
                                             (16, 48, (48, 50, 48), 1)])
 def test_conv3d_accumulate_into_existing_gradient(dtype, cin, cout, size, n):
-    """out += conv(x): the dgrad of the UpConv chain adds into a skip gradient (exec.hip conv_backward, accumulate=1).
+    """out += conv(x): the dgrad of the UpConv chain adds into a skip gradient (exec.hip conv_backward, ConvBwd::accumulate = 1).
     >= 48^3 runs the persistent kernel's non-deferred epilogue (batch 3: the tile list crosses samples)."""
     x, w = _mk((n, cin) + size, 11), _mk((cout, cin, 3, 3, 3), 12) * (cin * 27) ** -0.5
     base = _mk((n, cout) + size, 13)
