@@ -9,6 +9,7 @@
 #include "augment.h"
 #include "conv_igemm.h"
 #include "loss.h"
+#include "metrics.h"
 #include "optim.h"
 #include "transformer.h"
 #include "unet_ops.h"
@@ -338,7 +339,7 @@ int hdf_op_conv3d_wgrad(int dtype, int stride, const void* sm, int64_t sm_pitch,
 int hdf_op_in_finalize(const float* partials, int N, int tiles, int C, int CP, int64_t voxels, const float* gamma,
                        const float* beta, float eps, float* mean, float* rstd, float* scale, float* shift,
                        hdf_stream stream) {
-  return hdf_launch_in_finalize(partials, N, tiles, C, CP, voxels, gamma, beta, eps, mean, rstd, scale, shift,
+  return hdf_launch_in_finalize(partials, N, tiles, C, CP, voxels, gamma, beta, eps, NormStatsOut{scale, shift, mean, rstd},
                                 (hipStream_t)stream);
 }
 int64_t hdf_op_in_bwd_workspace_floats(int N, int C, int64_t voxels) {
@@ -352,14 +353,13 @@ int hdf_op_in_bwd(int dtype, const void* da, int64_t da_pitch, const void* y, in
   const int blocks = hdf_in_bwd_blocks(voxels, C);
   float* partials = workspace;
   float* k1 = workspace + (int64_t)N * blocks * C * 2;
-  float* ka = k1 + (int64_t)N * C;
-  float* kb = ka + (int64_t)N * C;
+  const InBwdCoefOut coef{k1, k1 + (int64_t)N * C, k1 + (int64_t)2 * N * C};
+  const NormStats ys{scale, shift, mean, rstd};
   hipStream_t st = (hipStream_t)stream;
-  HDF_TRY(hdf_launch_in_bwd_reduce(dtype, da, da_pitch, y, y_pitch, scale, shift, mean, rstd, partials, blocks, N, C,
-                                   voxels, st));
-  HDF_TRY(hdf_launch_in_bwd_finalize(partials, blocks, N, C, voxels, gamma, rstd, k1, ka, kb, dgamma, dbeta, st));
-  return hdf_launch_in_bwd_apply(dtype, da, da_pitch, y, y_pitch, scale, shift, mean, rstd, k1, ka, kb, dy, dy_pitch, N,
-                                 C, voxels, st);
+  HDF_TRY(hdf_launch_in_bwd_reduce(dtype, CRows{da, da_pitch}, CRows{y, y_pitch}, ys, partials, blocks, N, C, voxels, st));
+  HDF_TRY(hdf_launch_in_bwd_finalize(partials, blocks, N, C, voxels, gamma, rstd, coef, dgamma, dbeta, st));
+  return hdf_launch_in_bwd_apply(dtype, CRows{da, da_pitch}, CRows{y, y_pitch}, ys, coef, Rows{dy, dy_pitch}, N, C, voxels,
+                                 st);
 }
 int hdf_op_in_bwd_wgrad(int dtype, const void* da, int64_t da_pitch, const void* y, int64_t y_pitch, const float* scale,
                         const float* shift, const float* mean, const float* rstd, const float* gamma, void* dy,
@@ -390,40 +390,43 @@ int hdf_op_in_bwd_wgrad(int dtype, const void* da, int64_t da_pitch, const void*
                   Cin, Cout, D, H, W);
     return HDF_ERR_UNSUPPORTED;
   }
-  HDF_TRY(hdf_launch_in_bwd_reduce(dtype, da, da_pitch, y, y_pitch, scale, shift, mean, rstd, partials, blocks, N, Cout,
-                                   voxels, st));
-  HDF_TRY(hdf_launch_in_bwd_finalize(partials, blocks, N, Cout, voxels, gamma, rstd, k1, ka, kb, dgamma, dbeta, st));
+  HDF_TRY(hdf_launch_in_bwd_reduce(dtype, CRows{da, da_pitch}, CRows{y, y_pitch}, NormStats{scale, shift, mean, rstd},
+                                   partials, blocks, N, Cout, voxels, st));
+  HDF_TRY(hdf_launch_in_bwd_finalize(partials, blocks, N, Cout, voxels, gamma, rstd, InBwdCoefOut{k1, ka, kb}, dgamma, dbeta,
+                                     st));
   return hdf_launch_wgrad(dtype, 1, w, dw, Cout, Cin, 0, wgrad_workspace, (size_t)wgrad_workspace_bytes, st);
 }
 int hdf_op_norm_relu_add(int dtype, const void* y, int64_t y_pitch, const float* scale, const float* shift,
                          const void* skip, int64_t skip_pitch, void* out, int64_t out_pitch, int N, int C,
                          int64_t voxels, hdf_stream stream) {
-  return hdf_launch_norm_relu_add(dtype, y, y_pitch, scale, shift, skip, skip_pitch, out, out_pitch, N, C, voxels,
-                                  (hipStream_t)stream);
+  return hdf_launch_norm_relu_add(dtype, CRows{y, y_pitch}, NormStats{scale, shift}, CRows{skip, skip_pitch},
+                                  Rows{out, out_pitch}, N, C, voxels, (hipStream_t)stream);
 }
 int hdf_op_maxpool_fwd(int dtype, const void* in, int64_t in_pitch, void* out, int64_t out_pitch, uint8_t* idx, int N,
                        int C, int Do, int Ho, int Wo, hdf_stream stream) {
-  return hdf_launch_maxpool_fwd(dtype, in, in_pitch, out, out_pitch, idx, N, C, Do, Ho, Wo, (hipStream_t)stream);
+  return hdf_launch_maxpool_fwd(dtype, CRows{in, in_pitch}, Rows{out, out_pitch}, idx, Extent{N, C, Do, Ho, Wo},
+                                (hipStream_t)stream);
 }
 int hdf_op_enc_tail(int dtype, const void* y, int64_t y_pitch, const float* scale, const float* shift, const void* skip,
                     int64_t skip_pitch, void* ds, int64_t ds_pitch, void* pooled, int64_t pooled_pitch, uint8_t* idx,
                     int N, int C, int Do, int Ho, int Wo, hdf_stream stream) {
   HDF_CHECK_ARG(y && scale && shift && skip && ds && pooled && idx, "enc_tail: null argument");
-  return hdf_launch_enc_tail(dtype, y, y_pitch, scale, shift, skip, skip_pitch, ds, ds_pitch, pooled, pooled_pitch, idx, N,
-                             C, Do, Ho, Wo, (hipStream_t)stream);
+  return hdf_launch_enc_tail(dtype, CRows{y, y_pitch}, NormStats{scale, shift}, CRows{skip, skip_pitch}, Rows{ds, ds_pitch},
+                             Rows{pooled, pooled_pitch}, idx, Extent{N, C, Do, Ho, Wo}, (hipStream_t)stream);
 }
 int hdf_op_enc_tail_up(int dtype, const void* y, int64_t y_pitch, const float* scale, const float* shift, const void* low,
                        int64_t low_pitch, const float* lscale, const float* lshift, void* ds, int64_t ds_pitch,
                        void* pooled, int64_t pooled_pitch, uint8_t* idx, int N, int C, int Do, int Ho, int Wo,
                        hdf_stream stream) {
   HDF_CHECK_ARG(y && scale && shift && low && lscale && lshift && ds && pooled && idx, "enc_tail_up: null argument");
-  return hdf_launch_enc_tail_up(dtype, y, y_pitch, scale, shift, low, low_pitch, lscale, lshift, ds, ds_pitch, pooled,
-                                pooled_pitch, idx, N, C, Do, Ho, Wo, (hipStream_t)stream);
+  return hdf_launch_enc_tail_up(dtype, CRows{y, y_pitch}, NormStats{scale, shift}, CRows{low, low_pitch},
+                                NormStats{lscale, lshift}, Rows{ds, ds_pitch}, Rows{pooled, pooled_pitch}, idx,
+                                Extent{N, C, Do, Ho, Wo}, (hipStream_t)stream);
 }
 int hdf_op_maxpool_bwd(int dtype, const void* dout, int64_t dout_pitch, const uint8_t* idx, void* din,
                        int64_t din_pitch, int N, int C, int Do, int Ho, int Wo, int accumulate, hdf_stream stream) {
-  return hdf_launch_maxpool_bwd(dtype, dout, dout_pitch, idx, din, din_pitch, N, C, Do, Ho, Wo, accumulate,
-                                (hipStream_t)stream);
+  return hdf_launch_maxpool_bwd(dtype, CRows{dout, dout_pitch}, idx, Rows{din, din_pitch}, Extent{N, C, Do, Ho, Wo},
+                                accumulate, (hipStream_t)stream);
 }
 int hdf_op_maxpool_bwd_in_rows(int C, int Do, int Ho, int Wo) {
   return hdf_maxpool_bwd_in_blocks((int64_t)Do * Ho * Wo, C);
@@ -433,17 +436,19 @@ int hdf_op_maxpool_bwd_in(int dtype, const void* dout, int64_t dout_pitch, const
                           const float* mean, const float* rstd, float* partials, int N, int C, int Do, int Ho, int Wo,
                           hdf_stream stream) {
   HDF_CHECK_ARG(dout && idx && din && y && scale && shift && mean && rstd && partials, "maxpool_bwd_in: null argument");
-  return hdf_launch_maxpool_bwd_in(dtype, dout, dout_pitch, idx, din, din_pitch, y, y_pitch, scale, shift, mean, rstd,
-                                   partials, N, C, Do, Ho, Wo, (hipStream_t)stream);
+  return hdf_launch_maxpool_bwd_in(dtype, CRows{dout, dout_pitch}, idx, Rows{din, din_pitch}, CRows{y, y_pitch},
+                                   NormStats{scale, shift, mean, rstd}, partials, Extent{N, C, Do, Ho, Wo},
+                                   (hipStream_t)stream);
 }
 int hdf_op_upsample_fwd(int dtype, const void* y, int64_t y_pitch, const float* scale, const float* shift, void* out,
                         int64_t out_pitch, int N, int C, int Di, int Hi, int Wi, hdf_stream stream) {
-  return hdf_launch_upsample_fwd(dtype, y, y_pitch, scale, shift, out, out_pitch, N, C, Di, Hi, Wi,
-                                 (hipStream_t)stream);
+  return hdf_launch_upsample_fwd(dtype, CRows{y, y_pitch}, NormStats{scale, shift}, Rows{out, out_pitch},
+                                 Extent{N, C, Di, Hi, Wi}, (hipStream_t)stream);
 }
 int hdf_op_upsample_bwd(int dtype, const void* dout, int64_t dout_pitch, void* din, int64_t din_pitch, int N, int C,
                         int Di, int Hi, int Wi, hdf_stream stream) {
-  return hdf_launch_upsample_bwd(dtype, dout, dout_pitch, din, din_pitch, N, C, Di, Hi, Wi, (hipStream_t)stream);
+  return hdf_launch_upsample_bwd(dtype, CRows{dout, dout_pitch}, Rows{din, din_pitch}, Extent{N, C, Di, Hi, Wi},
+                                 (hipStream_t)stream);
 }
 
 
@@ -554,15 +559,16 @@ int hdf_op_head_fwd(int dtype, const void* in, int64_t in_pitch, const float* in
                     const float* weight, const float* bias, void* logits, int N, int C, int n_cls, int64_t voxels,
                     hdf_stream stream) {
   HDF_CHECK_ARG(in && weight && bias && logits, "head_fwd: null argument");
-  return hdf_launch_head_fwd(dtype, in, in_pitch, in_scale, in_shift, weight, bias, logits, N, C, n_cls, voxels,
-                             (hipStream_t)stream);
+  return hdf_launch_head_fwd(dtype, CRows{in, in_pitch}, NormStats{in_scale, in_shift}, weight, bias, logits, N, C, n_cls,
+                             voxels, (hipStream_t)stream);
 }
 int hdf_op_head_bwd(int dtype, const void* dlogits, const void* in, int64_t in_pitch, const float* in_scale,
                     const float* in_shift, const float* weight, void* dx, int64_t dx_pitch, int accumulate_dx,
                     float* dweight, float* dbias, int N, int C, int n_cls, int64_t voxels, hdf_stream stream) {
   HDF_CHECK_ARG(dlogits && in && weight && dx && dweight && dbias, "head_bwd: null argument");
-  return hdf_launch_head_bwd(dtype, dlogits, in, in_pitch, in_scale, in_shift, weight, dx, dx_pitch, accumulate_dx,
-                             dweight, dbias, N, C, n_cls, voxels, (hipStream_t)stream);
+  return hdf_launch_head_bwd(dtype, dlogits, CRows{in, in_pitch}, NormStats{in_scale, in_shift}, weight,
+                             HeadGrads{Rows{dx, dx_pitch}, accumulate_dx, dweight, dbias}, N, C, n_cls, voxels,
+                             (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,3 +1,4 @@
+// The device-side input pipeline (augment.hip): normalisation, one-hot staging, the 3-D training augmentation.
 #pragma once
 #include "hdf_common.h"
 
@@ -11,3 +12,9 @@ struct AugAffine {
 int hdf_launch_augment3d(const float* image, const uint8_t* labels, int C, int n_cls, int D, int H, int W,
                          const AugAffine& aff, int flip_h, int flip_w, float* image_out, uint8_t* labels_out,
                          float* onehot_out, hipStream_t st);
+
+// in-place input normalisation of one sample [C][V] fp32 (data_utils/data_loader.py:39-68); mode 0 MR, 1 PET/CT
+size_t hdf_norm_ws_bytes(int C);
+int hdf_launch_normalize(float* img, int C, int64_t V, int mode, float pmean, float pw, void* ws, hipStream_t st);
+// class maps [N][V] uint8 -> one-hot [N][C][V] fp32 (labels outside [1, C) count as background)
+int hdf_launch_onehot(const uint8_t* lab, float* oh, int N, int C, int64_t V, hipStream_t st);

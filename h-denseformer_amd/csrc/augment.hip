@@ -1,6 +1,8 @@
-// The reference's 3-D training augmentation on the device, one launch per sample: RandomTranslationRotationZoom3D
+// The device-side input pipeline: the in-place input normalisation of one sample (hdf_launch_normalize,
+// data_utils/data_loader.py:39-68), the one-hot staging of a batch of class maps (hdf_launch_onehot), and the reference's
+// 3-D training augmentation, one launch per sample (hdf_launch_augment3d): RandomTranslationRotationZoom3D
 // (data_utils/transformer_3d.py:45-120), RandomFlip3D (:123-169) and the To_Tensor one-hot (data_utils/data_loader.py:
-// 126-159).  A memory-bound gather: every output voxel reads the eight corners of its source coordinate, per image channel
+// 126-159).  The augmentation is a memory-bound gather: every output voxel reads the eight corners of its source coordinate, per image channel
 // and once for the labels.  The reference's angles are +-5 degrees, so a wave's 64 source addresses stay within a few rows
 // of one plane: the corners come from L2, nothing is staged through LDS.
 //
@@ -11,9 +13,10 @@
 #include <cmath>
 
 #include "augment.h"
+#include "loss.h"
 
 namespace {
-constexpr int AUG_MAXCLS = 8;   // SW_MAXC of loss.hip: the class slots of the staging and inference kernels
+constexpr int AUG_MAXCLS = HDF_CLASS_SLOTS;   // the class slots of the staging and inference kernels
 constexpr int AUG_MAXCH = 64;   // the cap of hdf_launch_normalize
 
 // one axis of the trilinear stencil: corner indices i0, i0 + 1, their weights 1 - f, f and whether each lies in [0, n).
@@ -103,6 +106,89 @@ augment3d_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab,
   }
 }
 
+// ---------------------------------------------------------------------------------- input normalisation
+// data_utils/data_loader.py:39-68.  Per-channel reductions over the volume in a fixed order (block partials in
+// fp64, then one block), then one elementwise pass.  stats[c] = (max, sum, sum of squares, unused).
+constexpr int NORM_BLOCKS = 512;
+__global__ __launch_bounds__(256) void norm_reduce_kernel(const float* __restrict__ img, int64_t V,
+                                                          double* __restrict__ part /*[C][NORM_BLOCKS][3]*/) {
+  __shared__ double red[4][3];
+  const int c = blockIdx.y;
+  const float* p = img + (int64_t)c * V;
+  double mx = -INFINITY, s = 0.0, ss = 0.0;
+  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (int64_t)gridDim.x * 256) {
+    const double x = (double)p[v];
+    mx = fmax(mx, x);
+    s += x;
+    ss += x * x;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mx = fmax(mx, __shfl_xor(mx, o, 64));
+    s += __shfl_xor(s, o, 64);
+    ss += __shfl_xor(ss, o, 64);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[wave][0] = mx, red[wave][1] = s, red[wave][2] = ss;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* o = part + ((int64_t)c * gridDim.x + blockIdx.x) * 3;
+    o[0] = fmax(fmax(red[0][0], red[1][0]), fmax(red[2][0], red[3][0]));
+    o[1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+    o[2] = red[0][2] + red[1][2] + red[2][2] + red[3][2];
+  }
+}
+__global__ void norm_finalize_kernel(const double* __restrict__ part, int blocks, int64_t V,
+                                     double* __restrict__ stats /*[C][4]: max, mean, std (population), 0*/) {
+  const int c = blockIdx.x;
+  if (threadIdx.x == 0) {
+    double mx = -INFINITY, s = 0.0, ss = 0.0;
+    for (int b = 0; b < blocks; b++) {
+      const double* q = part + ((int64_t)c * blocks + b) * 3;
+      mx = fmax(mx, q[0]);
+      s += q[1];
+      ss += q[2];
+    }
+    const double mean = s / (double)V;
+    stats[c * 4 + 0] = mx;
+    stats[c * 4 + 1] = mean;
+    stats[c * 4 + 2] = sqrt(fmax(ss / (double)V - mean * mean, 0.0));
+    stats[c * 4 + 3] = 0.0;
+  }
+}
+// mode 0 (MRNormalize, data_loader.py:39-50): x / max(channel) when the max is non-zero, then negatives -> 0.
+// mode 1 (PETandCTNormalize, :53-68): channel 0 -> (clip(x, mean-w, mean+w) - mean) / w ; channel 1 -> (x - mean_1)
+//         / (std_1 + 1e-3) ; further channels untouched.
+__global__ void norm_apply_kernel(float* __restrict__ img, int64_t V, const double* __restrict__ stats, int mode,
+                                  float pmean, float pw) {
+  const int c = blockIdx.y;
+  float* p = img + (int64_t)c * V;
+  const float mx = (float)stats[c * 4 + 0], mean = (float)stats[c * 4 + 1], sd = (float)stats[c * 4 + 2];
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < V; v += (int64_t)gridDim.x * blockDim.x) {
+    float x = p[v];
+    if (mode == 0) {
+      if (mx != 0.f) x = x / mx;
+      x = x < 0.f ? 0.f : x;
+    } else if (c == 0) {
+      x = (fminf(fmaxf(x, pmean - pw), pmean + pw) - pmean) / pw;
+    } else if (c == 1) {
+      x = (x - mean) / (sd + 1e-3f);
+    }
+    p[v] = x;
+  }
+}
+
+__global__ void onehot_kernel(const uint8_t* __restrict__ lab, float* __restrict__ oh, int C, int64_t V) {
+  const int n = blockIdx.y;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (int64_t)gridDim.x * blockDim.x) {
+    const int l = lab[(int64_t)n * V + i];
+    float* o = oh + (int64_t)n * C * V + i;
+    const bool fg = l >= 1 && l < C;
+    o[0] = fg ? 0.f : 1.f;
+    for (int c = 1; c < C; c++) o[(int64_t)c * V] = (l == c) ? 1.f : 0.f;
+  }
+}
+
 bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
   if (!a || !b) return false;
   const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
@@ -132,6 +218,31 @@ int hdf_launch_augment3d(const float* image, const uint8_t* labels, int C, int n
   const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64((int64_t)V, 256), 2048);
   hipLaunchKernelGGL(augment3d_kernel, dim3(gx), dim3(256), 0, st, image_out ? image : nullptr, labels, C, n_cls, D, H, W,
                      aff, flip_h != 0, flip_w != 0, image_out, labels_out, onehot_out);
+  HDF_LAUNCH_CHECK();
+  return HDF_OK;
+}
+
+size_t hdf_norm_ws_bytes(int C) { return ((size_t)C * NORM_BLOCKS * 3 + (size_t)C * 4) * sizeof(double); }
+int hdf_launch_normalize(float* img, int C, int64_t V, int mode, float pmean, float pw, void* ws, hipStream_t st) {
+  HDF_CHECK_ARG(C >= 1 && C <= 64 && V >= 1, "normalize: channels=%d voxels=%lld", C, (long long)V);
+  HDF_CHECK_ARG(mode == 0 || mode == 1, "normalize: mode %d", mode);
+  HDF_CHECK_ARG(mode == 0 || (C >= 2 && pw != 0.f), "normalize: PET/CT mode needs >= 2 channels and w != 0");
+  double* part = (double*)ws;
+  double* stats = part + (size_t)C * NORM_BLOCKS * 3;
+  hipLaunchKernelGGL(norm_reduce_kernel, dim3(NORM_BLOCKS, C), dim3(256), 0, st, img, V, part);
+  HDF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(norm_finalize_kernel, dim3(C), dim3(64), 0, st, part, NORM_BLOCKS, V, stats);
+  HDF_LAUNCH_CHECK();
+  unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(V, 256), 4096);
+  hipLaunchKernelGGL(norm_apply_kernel, dim3(gx, C), dim3(256), 0, st, img, V, stats, mode, pmean, pw);
+  HDF_LAUNCH_CHECK();
+  return HDF_OK;
+}
+
+int hdf_launch_onehot(const uint8_t* lab, float* oh, int N, int C, int64_t V, hipStream_t st) {
+  HDF_CHECK_ARG(C >= 2 && C <= 255 && N >= 1, "onehot: n_cls=%d batch=%d", C, N);
+  dim3 grid((unsigned)std::min<int64_t>(ceil_div64(V, 256), 4096), N);
+  hipLaunchKernelGGL(onehot_kernel, grid, dim3(256), 0, st, lab, oh, C, V);
   HDF_LAUNCH_CHECK();
   return HDF_OK;
 }

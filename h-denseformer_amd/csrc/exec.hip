@@ -62,8 +62,7 @@ int conv_forward(Exec& e, Conv3& c, const View& in, Xf xf, bool probe = false) {
   }
   int tiles = hdf_conv_stat_tiles(0, d[0], d[1], d[2], c.CinP * p->esz);
   HDF_TRY(hdf_launch_in_finalize(e.statp(), e.B, tiles, c.Cout, a.CoutP, p->vox(c.lvl), e.P(c.gamma),
-                                 e.P(c.beta), 1e-5f, e.f(c.st.mean), e.f(c.st.rstd), e.f(c.st.scale),
-                                 e.f(c.st.shift), e.st));
+                                 e.P(c.beta), 1e-5f, e.norm(c.st), e.st));
   return HDF_OK;
 }
 
@@ -75,7 +74,7 @@ int convt_forward(Exec& e, ConvT3& t, const View& in, Xf xf, const View& out) {
 }
 
 int head_forward(Exec& e, const Head1& h, const View& in, Xf xf, void* out) {
-  return hdf_launch_head_fwd(e.p->dtype, e.at(in), in.pitch, xf.scale, xf.shift, e.P(h.w), e.P(h.b), out, e.B, h.C,
+  return hdf_launch_head_fwd(e.p->dtype, e.rows(in), NormStats{xf.scale, xf.shift}, e.P(h.w), e.P(h.b), out, e.B, h.C,
                              e.p->ncls, e.p->vox(h.lvl), e.st);
 }
 
@@ -90,21 +89,15 @@ int in_backward(Exec& e, const Conv3& c, const View& da, const View& dy, const I
   const int64_t vox = p->vox(c.lvl);
   const int blocks = o.pre_blocks > 0 ? o.pre_blocks : hdf_in_bwd_blocks(vox, c.Cout);
   float* k = o.kbuf ? o.kbuf : e.inbk();
-  float* k1 = k;
-  float* ka = k + (size_t)e.B * c.Cout;
-  float* kb = k + (size_t)2 * e.B * c.Cout;
+  const InBwdCoefOut coef{k, k + (size_t)e.B * c.Cout, k + (size_t)2 * e.B * c.Cout};
   if (o.pre_blocks == 0)
-    HDF_TRY(hdf_launch_in_bwd_reduce(p->dtype, e.at(da), da.pitch, e.at(c.y), c.y.pitch, e.f(c.st.scale),
-                                     e.f(c.st.shift), e.f(c.st.mean), e.f(c.st.rstd), e.inbp(), blocks, e.B,
-                                     c.Cout, vox, e.st));
-  HDF_TRY(hdf_launch_in_bwd_finalize(e.inbp(), blocks, e.B, c.Cout, vox, e.P(c.gamma), e.f(c.st.rstd), k1,
-                                     ka, kb, e.G(c.gamma), e.G(c.beta), e.st));
+    HDF_TRY(hdf_launch_in_bwd_reduce(p->dtype, e.rows(da), e.rows(c.y), e.norm(c.st), e.inbp(), blocks, e.B, c.Cout, vox,
+                                     e.st));
+  HDF_TRY(hdf_launch_in_bwd_finalize(e.inbp(), blocks, e.B, c.Cout, vox, e.P(c.gamma), e.f(c.st.rstd), coef,
+                                     e.G(c.gamma), e.G(c.beta), e.st));
   if (!o.apply) return HDF_OK;
   e.wait_readers(dy);  // a side-stream weight gradient may still read this buffer's previous contents
-  HDF_TRY(hdf_launch_in_bwd_apply(p->dtype, e.at(da), da.pitch, e.at(c.y), c.y.pitch, e.f(c.st.scale), e.f(c.st.shift),
-                                  e.f(c.st.mean), e.f(c.st.rstd), k1, ka, kb, e.at(dy), dy.pitch, e.B, c.Cout, vox,
-                                  e.st));
-  return HDF_OK;
+  return hdf_launch_in_bwd_apply(p->dtype, e.rows(da), e.rows(c.y), e.norm(c.st), coef, e.rows(dy), e.B, c.Cout, vox, e.st);
 }
 
 // ap: dy has NOT been written yet.  ap->da is the gradient w.r.t. c's activation and in_backward(.., apply = false) has
@@ -271,10 +264,10 @@ int head_backward(Exec& e, const Head1& h, const void* dlogits, const View& in, 
   const int hb = hdf_head_bwd_blocks(p->vox(h.lvl));
   const bool fuse = o.fuse_in && o.pre_blocks && hb <= 1024;
   if (o.pre_blocks) *o.pre_blocks = fuse ? hb : 0;
-  return hdf_launch_head_bwd(p->dtype, dlogits, e.at(in), in.pitch, xf.scale, xf.shift, e.P(h.w), e.at(dx), dx.pitch,
-                             o.accumulate, e.G(h.w), e.G(h.b), e.B, h.C, p->ncls, p->vox(h.lvl), e.st,
-                             fuse ? e.f(o.fuse_in->st.mean) : nullptr, fuse ? e.f(o.fuse_in->st.rstd) : nullptr,
-                             fuse ? e.inbp() : nullptr);
+  NormStats ins{xf.scale, xf.shift};
+  HeadGrads g{e.rows(dx), o.accumulate, e.G(h.w), e.G(h.b)};
+  if (fuse) ins.mean = e.f(o.fuse_in->st.mean), ins.rstd = e.f(o.fuse_in->st.rstd), g.inb_partials = e.inbp();
+  return hdf_launch_head_bwd(p->dtype, dlogits, e.rows(in), ins, e.P(h.w), g, e.B, h.C, p->ncls, p->vox(h.lvl), e.st);
 }
 
 }  // namespace
@@ -299,11 +292,9 @@ static int upconv_chain_backward(Exec& e, int batch) {
   for (int k = 2; k >= 0; k--) {
     Conv3& c = p->up[k];                                   // up[k] output level c.lvl, upsampled to level c.lvl-1
     View dat = p->dSkip[c.lvl - 1];  // gradient of at_{..} == of ds
-    const int* d = p->dims[c.lvl];
     View& da = p->dUa[4 - c.lvl];
     View& dy = p->dUy[4 - c.lvl];
-    HDF_TRY(hdf_launch_upsample_bwd(p->dtype, e.at(dat), dat.pitch, e.at(da), da.pitch, batch, c.Cout, d[0], d[1], d[2],
-                                    e.st, p->flat ? 1 : 0));
+    HDF_TRY(hdf_launch_upsample_bwd(p->dtype, e.rows(dat), e.rows(da), e.extent(c.lvl, c.Cout), e.st));
     HDF_TRY(in_backward(e, c, da, dy));
     // input of up[k]: attnout (k==0) or at_{lvl} ; its gradient buffer already holds the skip-path gradient
     const View& cin = (k == 0) ? p->attnout : p->at[c.lvl];
@@ -314,9 +305,7 @@ static int upconv_chain_backward(Exec& e, int batch) {
   }
   {
     Conv3& c = p->deep;
-    const int* d = p->dims[4];
-    HDF_TRY(hdf_launch_upsample_bwd(p->dtype, e.at(p->dX4), p->dX4.pitch, e.at(p->dUa[0]), p->dUa[0].pitch, batch,
-                                    c.Cout, d[0], d[1], d[2], e.st, p->flat ? 1 : 0));
+    HDF_TRY(hdf_launch_upsample_bwd(p->dtype, e.rows(p->dX4), e.rows(p->dUa[0]), e.extent(4, c.Cout), e.st));
     HDF_TRY(in_backward(e, c, p->dUa[0], p->dUy[0]));
     ConvBwd o;
     o.din = &p->dAttnall;
@@ -353,7 +342,6 @@ static int forward3d(hdf_plan* p, const float* x, const float* params, void* wor
   if (bst) eb.st = bst, eb.on_branch = true;
   Rejoin rejoin{e, eb, bst != nullptr};  // error returns below: no branch-stream work unordered behind the caller's stream
   const bool fused_at3 = !p->flat;   // (the 2-D model: materialised at3 + the 2-D encoder tail)
-  const int flat = p->flat ? 1 : 0;
   // (round 5) Order of the first launches.  The first level-0 conv reads the fp32 weights itself (csrc/conv_first.hip) and
   // needs only the converted input, so where that kernel takes the layer the caller's stream starts with conversion +
   // conv, and the weight packs -- every conv's 16-bit panels and the persistent transformer kernel's fragment-major copies,
@@ -402,9 +390,8 @@ static int forward3d(hdf_plan* p, const float* x, const float* params, void* wor
   if (!chain_first) HDF_TRY(transformer_forward(eb, x));
   if (packed) HDF_TRY(e.wait(bst, packed, "the branch stream behind the weight packs"));
   HDF_TRY(conv_forward(eb, p->deep, p->attnall, none));
-  HDF_TRY(hdf_launch_upsample_fwd(p->dtype, eb.at(p->deep.y), p->deep.y.pitch, eb.f(p->deep.st.scale),
-                                  eb.f(p->deep.st.shift), eb.at(p->attnout), p->attnout.pitch, batch, 8 * nf,
-                                  p->dims[4][0], p->dims[4][1], p->dims[4][2], eb.st, flat));
+  HDF_TRY(hdf_launch_upsample_fwd(p->dtype, eb.rows(p->deep.y), eb.norm(p->deep.st), eb.rows(p->attnout),
+                                  eb.extent(4, 8 * nf), eb.st));
   {
     const View* src = &p->attnout;
     for (int k = 0; k < 3; k++) {  // up1 -> at1 (lvl 2), up2 -> at2 (lvl 1), up3 -> at3 (lvl 0)
@@ -413,9 +400,8 @@ static int forward3d(hdf_plan* p, const float* x, const float* params, void* wor
       const View& dst = p->at[2 - k];
       // at3 (k == 2) is not materialised: the level-0 encoder tail interpolates it from up3's output (enc_tail_up_kernel)
       if (k == 2 && fused_at3) break;
-      HDF_TRY(hdf_launch_upsample_fwd(p->dtype, eb.at(c.y), c.y.pitch, eb.f(c.st.scale), eb.f(c.st.shift), eb.at(dst),
-                                      dst.pitch, batch, c.Cout, p->dims[c.lvl][0], p->dims[c.lvl][1],
-                                      p->dims[c.lvl][2], eb.st, flat));
+      HDF_TRY(hdf_launch_upsample_fwd(p->dtype, eb.rows(c.y), eb.norm(c.st), eb.rows(dst), eb.extent(c.lvl, c.Cout),
+                                      eb.st));
       src = &dst;
     }
   }
@@ -436,19 +422,15 @@ static int forward3d(hdf_plan* p, const float* x, const float* params, void* wor
       // ds_k = relu(IN(y)) + at_k ; pooled = MaxPool(ds_k): one fused pass
       if (k == 0 && fused_at3) {
         Conv3& u = p->up[2];  // at3 = Upsample(relu(IN(up3 conv))), evaluated inside the pass
-        HDF_TRY(hdf_launch_enc_tail_up(p->dtype, e.at(c.y), c.y.pitch, e.f(c.st.scale), e.f(c.st.shift), e.at(u.y), u.y.pitch,
-                                       e.f(u.st.scale), e.f(u.st.shift), e.at(ds), ds.pitch, e.at(p->pooled[k]),
-                                       p->pooled[k].pitch, (uint8_t*)(e.ws + p->pool_idx[k]), batch, ch[k],
-                                       p->dims[k + 1][0], p->dims[k + 1][1], p->dims[k + 1][2], e.st));
+        HDF_TRY(hdf_launch_enc_tail_up(p->dtype, e.rows(c.y), e.norm(c.st), e.rows(u.y), e.norm(u.st), e.rows(ds),
+                                       e.rows(p->pooled[k]), (uint8_t*)(e.ws + p->pool_idx[k]), e.extent(k + 1, ch[k]),
+                                       e.st));
       } else
-      HDF_TRY(hdf_launch_enc_tail(p->dtype, e.at(c.y), c.y.pitch, e.f(c.st.scale), e.f(c.st.shift), e.at(p->at[k]),
-                                  p->at[k].pitch, e.at(ds), ds.pitch, e.at(p->pooled[k]), p->pooled[k].pitch,
-                                  (uint8_t*)(e.ws + p->pool_idx[k]), batch, ch[k], p->dims[k + 1][0], p->dims[k + 1][1],
-                                  p->dims[k + 1][2], e.st, flat));
+      HDF_TRY(hdf_launch_enc_tail(p->dtype, e.rows(c.y), e.norm(c.st), e.rows(p->at[k]), e.rows(ds), e.rows(p->pooled[k]),
+                                  (uint8_t*)(e.ws + p->pool_idx[k]), e.extent(k + 1, ch[k]), e.st));
       cur = &p->pooled[k];
     } else {
-      HDF_TRY(hdf_launch_norm_relu_add(p->dtype, e.at(c.y), c.y.pitch, e.f(c.st.scale), e.f(c.st.shift),
-                                       e.at(p->attnout), p->attnout.pitch, e.at(p->x4), p->x4.pitch, batch, ch[3],
+      HDF_TRY(hdf_launch_norm_relu_add(p->dtype, e.rows(c.y), e.norm(c.st), e.rows(p->attnout), e.rows(p->x4), batch, ch[3],
                                        p->vox(3), e.st));
     }
   }
@@ -576,10 +558,8 @@ static int backward3d(hdf_plan* p, const float* x, const float* params, void* wo
       // ds_k also feeds pool_{k+1}: with that gradient added d(ds_k) is complete, and the pass that adds it takes the first
       // pass of c2's InstanceNorm backward along (pre rows per sample in the partials table)
       pre = hdf_maxpool_bwd_in_blocks((int64_t)p->dims[k + 1][0] * p->dims[k + 1][1] * p->dims[k + 1][2], ch[k]);
-      HDF_TRY(hdf_launch_maxpool_bwd_in(p->dtype, e.at(p->dP[k]), p->dP[k].pitch, (const uint8_t*)(e.ws + p->pool_idx[k]),
-                                        e.at(dskip), dskip.pitch, e.at(c2.y), c2.y.pitch, e.f(c2.st.scale),
-                                        e.f(c2.st.shift), e.f(c2.st.mean), e.f(c2.st.rstd), e.inbp(), batch, ch[k],
-                                        p->dims[k + 1][0], p->dims[k + 1][1], p->dims[k + 1][2], e.st, p->flat ? 1 : 0));
+      HDF_TRY(hdf_launch_maxpool_bwd_in(p->dtype, e.rows(p->dP[k]), (const uint8_t*)(e.ws + p->pool_idx[k]), e.rows(dskip),
+                                        e.rows(c2.y), e.norm(c2.st), e.inbp(), e.extent(k + 1, ch[k]), e.st));
     }
     if (k == 0 && fork_ok) {
       // d(ds_0) = d(at3) is final.  What is left: (1) the UpConv chain backward, (2) the transformer branches' backward,

@@ -4,6 +4,7 @@
 #include <map>
 
 #include "plan_internal.h"
+#include "unet_ops.h"
 
 namespace hdf_internal {
 
@@ -132,6 +133,10 @@ struct Exec {
   }
   void* at(const View& v) const { return ws + v.off; }
   float* f(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+  // what the launchers of unet_ops.h take: a view's rows, a layer's InstanceNorm constants, C channels at a level's extent
+  Rows rows(const View& v) const { return Rows{at(v), v.pitch}; }
+  NormStatsOut norm(const Stats& s) const { return NormStatsOut{f(s.scale), f(s.shift), f(s.mean), f(s.rstd)}; }
+  Extent extent(int lvl, int C) const { return Extent{B, C, dm(lvl)[0], dm(lvl)[1], dm(lvl)[2], p->flat ? 1 : 0}; }
   const float* P(int64_t off) const { return off < 0 ? nullptr : params + off; }
   float* G(int64_t off) const { return off < 0 ? nullptr : grads + off; }
   const int* dm(int lvl) const { return p->dims[lvl]; }

@@ -1,0 +1,16 @@
+// The evaluation path (metrics.hip): the on-device Dice metric and the sliding-window inference tail.
+#pragma once
+#include "loss.h"  // HDF_CLASS_SLOTS
+
+// counts[n][c][3] = (|P=c & T=c|, |P=c|, |T=c|), n < N, c < HDF_CLASS_SLOTS
+int hdf_launch_dice_counts(int dtype, const void* logits, const float* target, int N, int C, int64_t V,
+                           unsigned long long* counts, hipStream_t st);
+// conf[t][p] (HDF_CLASS_SLOTS x HDF_CLASS_SLOTS) (+)= voxels of target class t predicted as p, from logits + one-hot ...
+int hdf_launch_confusion(int dtype, const void* logits, const float* target, int N, int C, int64_t V,
+                         unsigned long long* conf, int accumulate, hipStream_t st);
+// ... or from two uint8 class maps
+int hdf_launch_confusion_labels(const uint8_t* tgt, const uint8_t* pred, int C, int64_t n, unsigned long long* conf,
+                                int accumulate, hipStream_t st);
+int hdf_launch_sw_accumulate(int dtype, const void* logits, int C, int pd, int ph, int pw, float* psum, float* cnt,
+                             int D, int H, int W, int z0, int y0, int x0, hipStream_t st);
+int hdf_launch_sw_finalize(const float* psum, const float* cnt, int C, int64_t V, uint8_t* label, hipStream_t st);

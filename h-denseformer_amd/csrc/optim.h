@@ -20,7 +20,7 @@ struct OptimCtl {
 static_assert(sizeof(OptimCtl) == 32, "hdf.h: HDF_OPTIM_STATE_WORDS");
 
 // One element of torch.optim.Adam (L2 decay added to the gradient where `dec`).  The ONE copy of the arithmetic:
-// adam_kernel (loss.hip, hdf_adam_step) and optim_kernel (optim.hip, hdf_optim_step) both inline it, and
+// adam_kernel (hdf_adam_step) and optim_kernel (hdf_optim_step), both in optim.hip, inline it, and
 // tests/test_gpu_optim.py holds the two to the same bits.  The fusing is pinned (as in_bwd_elem, hdf_common.h): left to
 // -ffp-contract hipcc fused b2*v + ... in the vectorised kernel and not in the scalar one.  The two explicit fma are the
 // ones adam_kernel has always had.
@@ -42,3 +42,6 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
 int hdf_launch_optim(int rule, float* p, const float* g, float* s1, float* s2, const uint8_t* mask, int64_t n, float lr0,
                      float lr1, float wd0, float wd1, float b1, float b2, float eps, int nesterov, float gmul,
                      const float* grad_scale, const float* found_inf, int* step_state, hipStream_t st);
+// hdf_adam_step: one Adam step with the bias corrections of `step` formed on the host
+int hdf_launch_adam(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float b1,
+                    float b2, float eps, float wd, int step, float gscale, hipStream_t st);

@@ -92,6 +92,19 @@ __global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const
   }
 }
 
+// ---------------------------------------------------------------------------------- Adam
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                            float* __restrict__ v, const uint8_t* __restrict__ decay, int64_t n, float lr, float b1,
+                            float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_elem(pi, g[i], mi, vi, decay && decay[i], gscale, lr, b1, b2, eps, wd, bc1, bc2_sqrt);   // optim.h
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi;
+  }
+}
+
 }  // namespace
 
 int hdf_launch_optim(int rule, float* p, const float* g, float* s1, float* s2, const uint8_t* mask, int64_t n, float lr0,
@@ -126,6 +139,17 @@ int hdf_launch_optim(int rule, float* p, const float* g, float* s1, float* s2, c
   else if (rule == HDF_OPTIM_ADAMW) HDF_OPTIM_LAUNCH(HDF_OPTIM_ADAMW);
   else HDF_OPTIM_LAUNCH(HDF_OPTIM_SGD);
 #undef HDF_OPTIM_LAUNCH
+  HDF_LAUNCH_CHECK();
+  return HDF_OK;
+}
+
+int hdf_launch_adam(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float b1,
+                    float b2, float eps, float wd, int step, float gscale, hipStream_t st) {
+  float bc1 = 1.f - powf(b1, (float)step);
+  float bc2s = sqrtf(1.f - powf(b2, (float)step));
+  unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(n, 256), 4096);
+  hipLaunchKernelGGL(adam_kernel, dim3(gx), dim3(256), 0, st, p, g, m, v, decay, n, lr, b1, b2, eps, wd, bc1, bc2s,
+                     gscale);
   HDF_LAUNCH_CHECK();
   return HDF_OK;
 }

@@ -1,5 +1,5 @@
 """CPU side of tests/test_gpu_metrics_inference.py: seeded inputs past the grid caps of the metric, staging and
-inference-tail kernels of csrc/loss.hip, and plain counts / fp64 restatements to hold them to.  No GPU in here."""
+inference-tail kernels of csrc/metrics.hip and csrc/augment.hip, and plain counts / fp64 restatements to hold them to.  No GPU in here."""
 import functools
 
 import numpy as np

@@ -39,6 +39,10 @@ def test_the_library_holds_the_expected_kernel_families(ks):
     for T in ("bf16_t", "f16_t"):
         for xfl in ("true", "false"):
             assert "conv_wgrad2_kernel<%s, %s, true>" % (T, xfl) in ks
+    # one kernel per InstanceNorm-backward pass for every storage type: the fp32 route is these (and so under the gate below)
+    for T in ("float", "bf16_t", "f16_t"):
+        assert "in_bwd_reduce4_kernel<%s>" % T in ks and "in_bwd_apply4_kernel<%s>" % T in ks
+    assert not any(n.startswith(("in_bwd_reduce_kernel", "in_bwd_apply_kernel")) for n in ks)
     assert sorted(n for n in ks if n.startswith("conv_wr_kernel")) == [
         "conv_wr_kernel<bf16_t, 128, 1, 2, 4, false>", "conv_wr_kernel<f16_t, 128, 1, 2, 4, false>"]
 

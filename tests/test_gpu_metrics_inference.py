@@ -1,5 +1,5 @@
 """The metric, staging and inference-tail C entries of include/hdf.h called directly, past the grid caps of their kernels
-(csrc/loss.hip), where a wrong grid stride, an uncovered tail or a lost count would show -- the existing tests go through
+(csrc/metrics.hip, csrc/augment.hip), where a wrong grid stride, an uncovered tail or a lost count would show -- the existing tests go through
 the Python wrappers at 8^3 .. 12x20x24 voxels, inside one trip of every grid-stride loop:
   hdf_dice_counts, hdf_confusion_matrix (1024 x 256)   V = 63*65*67 = 274 365, N = 3, C = 5: exact integers against a CPU
       count of first-maximum argmaxes of the storage-rounded logits (16-bit logits x 0.25: exact ties are common);

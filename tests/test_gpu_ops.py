@@ -487,7 +487,7 @@ def test_conv3d_first_layer_weight_gradient(dtype, cin, cout, size, n, accumulat
                                              (2, 64, (8, 8, 16), 2)])
 def test_conv3d_first_layer_weight_gradient_with_the_norm_backward_inside(dtype, cin, cout, size, n):
     """hdf_op_conv3d_first_wgrad_in: the first layer's weight gradient from d(activation) and y, with the apply pass of the
-    InstanceNorm(+ReLU) backward (unet_ops.hip in_bwd_apply4_kernel) evaluated on the staged rows -- against the two-step
+    InstanceNorm(+ReLU) backward (norm_ops.hip in_bwd_apply4_kernel) evaluated on the staged rows -- against the two-step
     path: dy by that formula in torch (rounded to the storage type), then hdf_op_conv3d_first_wgrad on it."""
     x = rnd(_mk((n, cin) + size, 71), dtype)
     da, y = rnd(_mk((n, cout) + size, 72), dtype), rnd(_mk((n, cout) + size, 73), dtype)
@@ -619,9 +619,12 @@ def test_encoder_tail_with_upsampling_inside_vs_torch(dtype, c, size):
 
 
 @pytest.mark.parametrize("dtype", [F32, BF16, F16])
-@pytest.mark.parametrize("n,c,size", [(2, 32, (8, 12, 16)), (1, 64, (20, 16, 24)), (2, 16, (32, 32, 36))])
+@pytest.mark.parametrize("n,c,size", [(2, 32, (8, 12, 16)), (1, 64, (20, 16, 24)), (2, 16, (32, 32, 36)),
+                                      (1, 48, (9, 10, 11))])
 def test_instance_norm_relu_backward(dtype, n, c, size):
-    """hdf_op_in_bwd (reduce + finalize + apply) vs autograd of relu(InstanceNorm3d(affine)(y)) (HDenseFormer.py:152-158)."""
+    """hdf_op_in_bwd (reduce + finalize + apply) vs autograd of relu(InstanceNorm3d(affine)(y)) (HDenseFormer.py:152-158).
+    (1, 48, (9, 10, 11)): 12 chunk lanes, so 21 voxel lanes and 4 idle threads; 990 voxels in 2 rows of 495, no multiple of
+    the 84 voxels an iteration covers, so both streaming passes run their clamped-load / masked-tail path."""
     y = rnd(_mk((n, c) + size, 21), dtype).requires_grad_(True)
     gamma, beta = (_mk((c,), 22) * 0.3 + 1.0).requires_grad_(True), (_mk((c,), 23) * 0.2).requires_grad_(True)
     da = rnd(_mk((n, c) + size, 24), dtype)
