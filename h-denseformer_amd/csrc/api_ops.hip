@@ -1,5 +1,5 @@
 // Process state (last error, compute-unit budget) and the one-to-one C ABI wrappers of the operator launchers: losses,
-// metrics, normalisation, sliding window, augmentation, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
+// metrics, surface distances, normalisation, sliding window, augmentation, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
 #include <atomic>
 #include <algorithm>
 #include <cstdarg>
@@ -11,6 +11,7 @@
 #include "loss.h"
 #include "metrics.h"
 #include "optim.h"
+#include "surface.h"
 #include "transformer.h"
 #include "unet_ops.h"
 
@@ -144,6 +145,40 @@ int hdf_confusion_matrix_labels(const uint8_t* target, const uint8_t* prediction
   HDF_CHECK_ARG(target && prediction && confusion, "confusion_matrix_labels: null argument");
   return hdf_launch_confusion_labels(target, prediction, n_cls, n, (unsigned long long*)confusion, accumulate,
                                      (hipStream_t)stream);
+}
+int64_t hdf_surface_workspace_bytes(int D, int H, int W) {
+  if (hdf_surface_check_dims("workspace_bytes", D, H, W) != HDF_OK) return -1;
+  return hdf_surface_ws_bytes(D, H, W);
+}
+int hdf_op_mask_flags(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W, uint8_t* flags,
+                      uint64_t* counts, hdf_stream stream) {
+  HDF_TRY(hdf_surface_check_dims("mask_flags", D, H, W));
+  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: mask_flags: label %d (1..255)", label);
+  HDF_CHECK_ARG(target && prediction && flags && counts, "surface: mask_flags: null argument");
+  return hdf_launch_mask_flags(target, prediction, label, D, H, W, flags, (unsigned long long*)counts, false,
+                               (hipStream_t)stream);
+}
+int hdf_op_edt_sq(const uint8_t* flags, int seed_bit, int D, int H, int W, int32_t* d2, void* workspace,
+                  int64_t workspace_bytes, hdf_stream stream) {
+  HDF_TRY(hdf_surface_check_dims("edt_sq", D, H, W));
+  HDF_CHECK_ARG(seed_bit >= 1 && seed_bit <= 255, "surface: edt_sq: seed mask %d (1..255)", seed_bit);
+  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_ws_bytes(D, H, W), "surface: edt_sq: workspace of %lld bytes, %lld needed",
+                (long long)workspace_bytes, (long long)hdf_surface_ws_bytes(D, H, W));
+  HDF_CHECK_ARG(flags && d2 && workspace, "surface: edt_sq: null argument");
+  return hdf_launch_edt_sq(flags, seed_bit, D, H, W, d2, (hipStream_t)stream);
+}
+int hdf_surface_distances(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
+                          void* workspace, int64_t workspace_bytes, uint64_t* result, uint32_t* histogram_out,
+                          int64_t histogram_len, hdf_stream stream) {
+  HDF_TRY(hdf_surface_check_dims("distances", D, H, W));
+  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: distances: label %d (1..255)", label);
+  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_ws_bytes(D, H, W),
+                "surface: distances: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+                (long long)hdf_surface_ws_bytes(D, H, W));
+  HDF_CHECK_ARG(histogram_len >= 0, "surface: distances: histogram_len %lld", (long long)histogram_len);
+  HDF_CHECK_ARG(target && prediction && workspace && result, "surface: distances: null argument");
+  return hdf_launch_surface_distances(target, prediction, label, D, H, W, workspace, (unsigned long long*)result,
+                                      histogram_out, histogram_len, (hipStream_t)stream);
 }
 int64_t hdf_normalize_workspace_bytes(int channels) { return (int64_t)hdf_norm_ws_bytes(channels); }
 int hdf_normalize_mr(float* image, int channels, int64_t voxels, void* workspace, hdf_stream stream) {

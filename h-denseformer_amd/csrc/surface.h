@@ -1,0 +1,31 @@
+// Surface-distance evaluation (surface.hip): mask flags, the exact squared Euclidean distance transform, the gather of
+// surface distances into a histogram and the order-statistic select.  Definitions: include/hdf.h.
+#pragma once
+#include "../../include/hdf.h"  // HDF_EDT_NO_SEED
+#include "hdf_common.h"
+
+// flag byte of one voxel (hdf_op_mask_flags)
+enum {
+  HDF_SF_IN_T = 1,    // target == label
+  HDF_SF_IN_P = 2,    // prediction == label
+  HDF_SF_B26_T = 4,   // in T with an in-volume 26-neighbour outside T: the seeds of d2_T
+  HDF_SF_B26_P = 8,
+  HDF_SF_C6_T = 16,   // in T with an in-volume face neighbour outside T: the contour
+  HDF_SF_C6_P = 32,
+};
+// "no seed anywhere" is HDF_EDT_NO_SEED (include/hdf.h): + 1023^2 = 1 074 788 352 < 2^31, and every real squared
+// distance (at most 3 * 1023^2) is below it
+constexpr int HDF_SURFACE_MAX_DIM = 1024;
+
+// host-side argument check shared by the entries: HDF_ERR_ARG with a "surface:" message
+int hdf_surface_check_dims(const char* who, int D, int H, int W);
+int64_t hdf_surface_ws_bytes(int D, int H, int W);
+// bins of the squared-distance histogram: (D-1)^2 + (H-1)^2 + (W-1)^2 + 1
+int64_t hdf_surface_hist_bins(int D, int H, int W);
+
+// counts_are_zero: the caller has cleared counts[5] on the stream already
+int hdf_launch_mask_flags(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, uint8_t* flags,
+                          unsigned long long* counts, bool counts_are_zero, hipStream_t st);
+int hdf_launch_edt_sq(const uint8_t* flags, int seed_mask, int D, int H, int W, int32_t* d2, hipStream_t st);
+int hdf_launch_surface_distances(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, void* ws,
+                                 unsigned long long* result, uint32_t* hist_out, int64_t hist_len, hipStream_t st);

@@ -2,6 +2,7 @@
 from ._lib import BF16, F32, EXPORTS, HdfError, LIB_PATH, lib  # noqa: F401
 
 _AUGMENT = ("TrainTransform3D", "augment_3d", "crop_origin", "flip_flags", "trz_matrix")
+_SURFACE = ("cal_score", "multi_dice", "multi_hd", "multi_jc", "multi_vs", "surface_scores")
 
 
 def __getattr__(name):
@@ -9,8 +10,11 @@ def __getattr__(name):
     if name in _AUGMENT:
         from . import augment
         return getattr(augment, name)
+    if name in _SURFACE:
+        from . import surface
+        return getattr(surface, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def __dir__():
-    return sorted(list(globals()) + list(_AUGMENT))
+    return sorted(list(globals()) + list(_AUGMENT) + list(_SURFACE))

@@ -1,0 +1,111 @@
+"""Scoring a label map against the ground truth on the device (reference: cal_score, multi_dice, multi_hd, multi_vs,
+multi_jc, metrics.py:156-309).  The reference makes one SimpleITK pass per class on the host -- overlap measures, two
+signed Maurer distance maps, two label contours, a percentile over the surface distances.  Here a class is one
+hdf_surface_distances call (mask flags, two exact squared distance transforms, a histogram, a select: csrc/surface.hip)
+that leaves twelve integers on the device; all classes are enqueued, the rows come back in ONE copy and the floats are
+formed in fp64 on the host.  Definitions: include/hdf.h.  No CPU fallback."""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, lib, ptr, stream_ptr
+
+KEYS = ("Jaccard", "Dice", "VolumeSimilarity", "HausdorffDistance", "HausdorffDistance95")
+# (device, stream, D, H, W) -> uint8 tensor: one workspace per volume shape and stream.  A workspace is reused by the next
+# call on ITS stream (the kernels of two calls are ordered there); callers on two streams get one each and do not race.
+# About 9 bytes a voxel plus the histogram; nothing is evicted -- clear_workspaces() gives the memory back.
+_workspaces = {}
+
+
+def clear_workspaces():
+    """drop the cached workspaces (a caller that is done scoring, or moves on to another volume shape)"""
+    _workspaces.clear()
+
+
+def _volume(a, what):
+    """uint8 [D][H][W] on the GPU from a device tensor or a numpy array (uploaded once)"""
+    if not torch.cuda.is_available():
+        raise _lib.HdfError("surface metrics need a GPU (there is no CPU path)")
+    if not torch.is_tensor(a):
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    if a.dim() != 3:
+        raise ValueError(f"{what} must be [D, H, W], got {tuple(a.shape)}")
+    if a.device.type != "cuda":
+        a = a.to("cuda")
+    return a.to(torch.uint8).contiguous()
+
+
+def _workspace(dev, shape):
+    key = (str(dev), stream_ptr()) + shape
+    ws = _workspaces.get(key)
+    if ws is None:
+        n = lib().hdf_surface_workspace_bytes(*shape)
+        if n < 0:
+            raise _lib.HdfError("hdf_surface_workspace_bytes: " + lib().hdf_last_error().decode(errors="replace"))
+        ws = _workspaces[key] = torch.empty(n, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def scores_from_result(row):
+    """the five numbers of cal_score in fp64 from one result[12] row of hdf_surface_distances"""
+    nT, nP, nI, _c6t, _c6p, hd2, _n, slo, shi, _lo, r, valid = (int(v) for v in row)
+    nan = float("nan")
+    out = {"Jaccard": nI / (nT + nP - nI) if nT + nP - nI else nan,
+           "Dice": 2 * nI / (nT + nP) if nT + nP else nan,
+           "VolumeSimilarity": 2 * (nT - nP) / (nT + nP) if nT + nP else nan,   # Execute(target, predict): target is ITK's source
+           "HausdorffDistance": nan, "HausdorffDistance95": nan}
+    if valid:
+        a, b = math.sqrt(slo), math.sqrt(shi)
+        out["HausdorffDistance"] = math.sqrt(hd2)
+        out["HausdorffDistance95"] = a + (b - a) * r / 100    # np.percentile(., 95), linear
+    return out
+
+
+def surface_scores(target, prediction, labels):
+    """one dict of KEYS per label in `labels` (each 1..255), for two uint8 volumes [D, H, W]"""
+    tgt, prd = _volume(target, "target"), _volume(prediction, "prediction")
+    if prd.device != tgt.device:
+        prd = prd.to(tgt.device)
+    if tgt.shape != prd.shape:
+        raise ValueError(f"target {tuple(tgt.shape)} and prediction {tuple(prd.shape)} differ")
+    labels = [int(k) for k in labels]
+    shape = tuple(int(s) for s in tgt.shape)
+    with torch.cuda.device(tgt.device):
+        ws = _workspace(tgt.device, shape)
+        rows = torch.empty((max(len(labels), 1), 12), dtype=torch.int64, device=tgt.device)
+        for i, k in enumerate(labels):
+            check(lib().hdf_surface_distances(ptr(tgt), ptr(prd), k, *shape, ptr(ws), ws.numel(), ptr(rows[i]), None, 0,
+                                              stream_ptr()), "hdf_surface_distances")
+        host = rows.cpu()          # the one D2H copy, after every class is enqueued
+    return [scores_from_result(host[i].tolist()) for i in range(len(labels))]
+
+
+def cal_score(predict, target):
+    """metrics.cal_score(predict, target) for two boolean or uint8 masks (non-zero = inside): a dict of KEYS.  The
+    reference's FalseNegativeError / FalsePositiveError are left out (none of its wrappers reads them)."""
+    prd, tgt = _volume(predict, "predict"), _volume(target, "target")
+    return surface_scores((tgt != 0).to(torch.uint8), (prd != 0).to(torch.uint8), [1])[0]
+
+
+def _multi(key, y_true, y_pred, num_classes):
+    vals = [round(s[key], 4) for s in surface_scores(y_true, y_pred, range(1, num_classes + 1))]
+    return vals, round(np.mean(vals), 4)
+
+
+def multi_dice(y_true, y_pred, num_classes):
+    return _multi("Dice", y_true, y_pred, num_classes)
+
+
+def multi_hd(y_true, y_pred, num_classes):
+    """per-class HausdorffDistance95, like the reference's multi_hd"""
+    return _multi("HausdorffDistance95", y_true, y_pred, num_classes)
+
+
+def multi_vs(y_true, y_pred, num_classes):
+    return _multi("VolumeSimilarity", y_true, y_pred, num_classes)
+
+
+def multi_jc(y_true, y_pred, num_classes):
+    return _multi("Jaccard", y_true, y_pred, num_classes)

@@ -224,6 +224,37 @@ int hdf_confusion_matrix(int dtype, const void* logits, const float* target_oneh
 int hdf_confusion_matrix_labels(const uint8_t* target, const uint8_t* prediction, int n_cls, int64_t n,
                                 uint64_t* confusion, int accumulate, hdf_stream stream);
 
+/* ---- surface-distance evaluation of one class (metrics.py:156-309, cal_score and the multi_* wrappers; the reference
+ * makes one SimpleITK pass per class on the host).  T = (target == label), P = (prediction == label) over one uint8
+ * volume [D][H][W], unit spacing; a neighbour outside the volume does not exist (it is never background).
+ * hdf_op_mask_flags: flags[v] = 1 v in T | 2 v in P | 4 v in B26(T) | 8 v in B26(P) | 16 v in C6(T) | 32 v in C6(P).
+ * B26(M): voxels of M with an in-volume 26-neighbour outside M (the seeds of ITK's Maurer filter); C6(M): voxels of M with
+ * an in-volume face neighbour outside M (sitk.LabelContour's default).  counts[5] uint64 = |T| |P| |T&P| |C6(T)| |C6(P)|.
+ * hdf_op_edt_sq: d2[v] int32 = min over the voxels b with (flags[b] & seed_bit) of |v - b|^2, exact;
+ * HDF_EDT_NO_SEED where the volume holds no such voxel.  seed_bit is a mask, 1..255.  The entry checks the workspace
+ * size like hdf_surface_distances (one allocation serves both) and does not touch it: the transform runs in place.
+ * hdf_surface_distances: the flags, d2_T (seeds B26(T)) and d2_P (seeds B26(P)), then
+ * result[12] uint64 = |T| |P| |T&P| |C6(T)| |C6(P)| hd2 n S[lo] S[hi] lo r valid, where
+ *   valid = neither T nor P is empty or fills the volume; when 0, hd2 .. r are 0 (the caller reports NaN);
+ *   hd2   = max(max over P\T of d2_T, max over T\P of d2_P, 0): HausdorffDistance = sqrt(hd2);
+ *   S     = the sorted multiset { d2_T(v) : v in C6(P) } + { d2_P(v) : v in C6(T) }, n = |S|, q = 95 (n - 1),
+ *           lo = q div 100, r = q mod 100, hi = min(lo + (r > 0), n - 1):
+ *           HausdorffDistance95 = sqrt(S[lo]) + (sqrt(S[hi]) - sqrt(S[lo])) r / 100 (np.percentile(., 95), linear).
+ * histogram_out (nullable, device): the count of every squared distance in S, histogram_len entries (those past
+ * (D-1)^2 + (H-1)^2 + (W-1)^2 are 0).  All pointers are device memory; the kernels are ordered on `stream`, nothing waits
+ * on the host, and a workspace may be reused by the next call on the same stream.  Refused (HDF_ERR_ARG, message
+ * "surface: ...") before anything is launched: a dimension outside 1..1024, D*H*W >= 2^31, label outside 1..255,
+ * a workspace below hdf_surface_workspace_bytes(D, H, W) (-1 for refused dimensions). */
+#define HDF_EDT_NO_SEED 0x3FFFFFFF /* + 1023^2 stays below 2^31 */
+int64_t hdf_surface_workspace_bytes(int D, int H, int W);
+int hdf_op_mask_flags(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
+                      uint8_t* flags, uint64_t* counts, hdf_stream stream);
+int hdf_op_edt_sq(const uint8_t* flags, int seed_bit, int D, int H, int W, int32_t* d2, void* workspace,
+                  int64_t workspace_bytes, hdf_stream stream);
+int hdf_surface_distances(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
+                          void* workspace, int64_t workspace_bytes, uint64_t* result, uint32_t* histogram_out,
+                          int64_t histogram_len, hdf_stream stream);
+
 /* ---- input normalisation on the device, in place on one fp32 sample [channels][voxels] -----------------------
  * hdf_normalize_mr: MRNormalize (data_utils/data_loader.py:39-50): every channel divided by its maximum when that is
  * non-zero, then negatives clamped to 0.  hdf_normalize_petct: PETandCTNormalize (:53-68): channel 0 ->
