@@ -215,6 +215,15 @@ int hdf_augment_3d(const float* image, const uint8_t* labels, int channels, int 
   return hdf_launch_augment3d(image, labels, channels, n_cls, D, H, W, a, flip_h, flip_w, image_out, labels_out,
                               onehot_out, (hipStream_t)stream);
 }
+int hdf_augment_2d(const float* image, const uint8_t* labels, int batch, int channels, int n_cls, int H, int W,
+                   const double* matrices, const uint8_t* flips, float* image_out, uint8_t* labels_out, float* onehot_out,
+                   hdf_stream stream) {
+  HDF_CHECK_ARG(matrices, "augment_2d: null matrices");
+  HDF_CHECK_ARG(flips, "augment_2d: null flips");
+  // both host arrays are copied into the kernel arguments chunk by chunk: the caller may reuse them at once
+  return hdf_launch_augment2d(image, labels, batch, channels, n_cls, H, W, matrices, flips, image_out, labels_out,
+                              onehot_out, (hipStream_t)stream);
+}
 int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   float grad_scale, hdf_stream stream) {

@@ -2,7 +2,8 @@
 // data_utils/data_loader.py:39-68), the one-hot staging of a batch of class maps (hdf_launch_onehot), and the reference's
 // 3-D training augmentation, one launch per sample (hdf_launch_augment3d): RandomTranslationRotationZoom3D
 // (data_utils/transformer_3d.py:45-120), RandomFlip3D (:123-169) and the To_Tensor one-hot (data_utils/data_loader.py:
-// 126-159).  The augmentation is a memory-bound gather: every output voxel reads the eight corners of its source coordinate, per image channel
+// 126-159), and the default 2-D one, one launch per 32 samples (hdf_launch_augment2d, further down): RandomRotate2D +
+// RandomFlip2D + To_Tensor (data_utils/transformer_2d.py:80-173).  The 3-D augmentation is a memory-bound gather: every output voxel reads the eight corners of its source coordinate, per image channel
 // and once for the labels.  The reference's angles are +-5 degrees, so a wave's 64 source addresses stay within a few rows
 // of one plane: the corners come from L2, nothing is staged through LDS.
 //
@@ -101,6 +102,77 @@ augment3d_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab,
         // To_Tensor: channel 0 is "no other class"
         oh_out[i] = res == 0 ? 1.f : 0.f;
         for (int zc = 1; zc < n_cls; zc++) oh_out[(int64_t)zc * V + i] = res == zc ? 1.f : 0.f;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------- 2-D training augmentation
+// RandomRotate2D + RandomFlip2D + To_Tensor (data_utils/transformer_2d.py:80-173) for a chunk of up to AUG2D_CHUNK
+// samples in one launch, bit for bit what PIL computes (include/hdf.h, hdf_augment_2d): the image through PIL's
+// affine_transform + bilinear_filter32F in fp64 with ONE fp32 subtraction per row, the labels through its 16.16
+// fixed-point affine_fixed.  Each thread works out the stencil of one output pixel once -- two rows, two clamped columns,
+// dx, dy, the label index -- and then walks the channels.  A memory-bound gather like the 3-D kernel: at +-15 degrees a
+// wave's 64 sources span a handful of rows of one plane, which L2 serves; nothing is staged through LDS.
+// The per-sample parameters travel BY VALUE in the kernel arguments (104 bytes a sample, 32 samples under the 4 KB
+// limit): the host arrays are read during the call and no staging buffer has a lifetime to manage.
+__global__ void __launch_bounds__(256)
+augment2d_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab, int nb, int C, int n_cls, int H, int W,
+                 Aug2DChunk prm, float* __restrict__ img_out, uint8_t* __restrict__ lab_out,
+                 float* __restrict__ oh_out) {
+  const int64_t P = (int64_t)H * W, total = (int64_t)nb * P;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    // a fused multiply-add anywhere below changes bits: PIL's build rounds every product
+#pragma clang fp contract(off)
+    const int b = (int)(i / P);
+    const int64_t r = i - (int64_t)b * P;
+    const int y = (int)(r / W), x = (int)(r - (int64_t)y * W);
+    const Aug2DSample& s = prm.s[b];
+    // the flip follows the rotation: out[y][x] = rotated[y][W-1-x] (1) or rotated[H-1-y][x] (2)
+    const int px = s.flip == 1 ? W - 1 - x : x, py = s.flip == 2 ? H - 1 - y : y;
+    if (img_out) {
+      const double xc = px + 0.5, yc = py + 0.5;
+      double xin = s.m[0] * xc + s.m[1] * yc + s.m[2];
+      double yin = s.m[3] * xc + s.m[4] * yc + s.m[5];
+      const bool inside = !(xin < 0.0 || xin >= (double)W || yin < 0.0 || yin >= (double)H);
+      // inside: xin - 0.5 lies in [-0.5, W - 0.5), its floor in [-1, W - 1]; outside nothing is loaded
+      xin -= 0.5, yin -= 0.5;
+      const double fx = floor(xin), fy = floor(yin);
+      const double dx = xin - fx, dy = yin - fy;
+      const int x0 = inside ? (int)fx : 0, y0 = inside ? (int)fy : 0;
+      const int xa = min(max(x0, 0), W - 1), xb = min(max(x0 + 1, 0), W - 1);
+      const int64_t row1 = (int64_t)min(max(y0, 0), H - 1) * W;
+      const bool below = y0 + 1 >= 0 && y0 + 1 < H;
+      const int64_t row2 = below ? (int64_t)(y0 + 1) * W : row1;
+      for (int c = 0; c < C; c++) {
+        const int64_t plane = ((int64_t)b * C + c) * P;
+        float res = 0.f;
+        if (inside) {
+          const float* src = img + plane;
+          const float p0 = src[row1 + xa], p1 = src[row1 + xb];
+          const double v1 = (double)p0 + (double)(p1 - p0) * dx;   // the neighbour difference is an fp32 subtraction
+          double v2 = v1;
+          if (below) {
+            const float q0 = src[row2 + xa], q1 = src[row2 + xb];
+            v2 = (double)q0 + (double)(q1 - q0) * dx;
+          }
+          res = (float)(v1 + (v2 - v1) * dy);
+        }
+        img_out[plane + r] = res;
+      }
+    }
+    if (lab_out || oh_out) {
+      // closed form of PIL's running sums: exact integers, arithmetic shift
+      const int64_t xi = (s.fx[2] + py * s.fx[1] + px * s.fx[0]) >> 16;
+      const int64_t yi = (s.fx[5] + py * s.fx[4] + px * s.fx[3]) >> 16;
+      const bool in_l = xi >= 0 && xi < W && yi >= 0 && yi < H;
+      const int l = in_l ? (int)lab[(int64_t)b * P + yi * W + xi] : 0;
+      if (lab_out) lab_out[i] = (uint8_t)l;   // the raw byte moves unchanged
+      if (oh_out) {
+        // To_Tensor: channel 0 is "no other class", a value >= n_cls is background
+        float* o = oh_out + (int64_t)b * n_cls * P + r;
+        o[0] = (l >= 1 && l < n_cls) ? 0.f : 1.f;
+        for (int zc = 1; zc < n_cls; zc++) o[(int64_t)zc * P] = l == zc ? 1.f : 0.f;
       }
     }
   }
@@ -219,6 +291,70 @@ int hdf_launch_augment3d(const float* image, const uint8_t* labels, int C, int n
   hipLaunchKernelGGL(augment3d_kernel, dim3(gx), dim3(256), 0, st, image_out ? image : nullptr, labels, C, n_cls, D, H, W,
                      aff, flip_h != 0, flip_w != 0, image_out, labels_out, onehot_out);
   HDF_LAUNCH_CHECK();
+  return HDF_OK;
+}
+
+// FIX of PIL's affine_fixed: 16.16, round half up
+static int64_t fix16(double v) {
+#pragma clang fp contract(off)
+  return (int64_t)std::floor(v * 65536.0 + 0.5);
+}
+
+int hdf_launch_augment2d(const float* image, const uint8_t* labels, int B, int C, int n_cls, int H, int W,
+                         const double* matrices, const uint8_t* flips, float* image_out, uint8_t* labels_out,
+                         float* onehot_out, hipStream_t st) {
+  HDF_CHECK_ARG(B >= 1, "augment_2d: batch=%d", B);
+  HDF_CHECK_ARG(H >= 1 && W >= 1 && H <= 16384 && W <= 16384, "augment_2d: plane %dx%d (1..16384 a side)", H, W);
+  HDF_CHECK_ARG(n_cls >= 2 && n_cls <= AUG_MAXCLS, "augment_2d: n_cls=%d (2..%d)", n_cls, AUG_MAXCLS);
+  HDF_CHECK_ARG(image_out || labels_out || onehot_out, "augment_2d: no output asked for");
+  HDF_CHECK_ARG(!image_out || (image && C >= 1 && C <= AUG_MAXCH),
+                "augment_2d: an image output needs an image of 1..%d channels (channels=%d)", AUG_MAXCH, C);
+  HDF_CHECK_ARG(labels || (!labels_out && !onehot_out), "augment_2d: a label output without labels");
+  HDF_CHECK_ARG(matrices && flips, "augment_2d: null %s", matrices ? "flips" : "matrices");
+  for (int b = 0; b < B; b++) {
+#pragma clang fp contract(off)
+    const double* m = matrices + 6 * (size_t)b;
+    for (int k = 0; k < 6; k++)
+      HDF_CHECK_ARG(std::isfinite(m[k]), "augment_2d: matrices[%d][%d] is not finite", b, k);
+    // PIL's check_fixed at the four corners: past it PIL leaves the 16.16 path, so the label contract would not hold
+    const int cx[4] = {0, W, 0, W}, cy[4] = {0, 0, H, H};
+    for (int k = 0; k < 4; k++)
+      HDF_CHECK_ARG(std::fabs(cx[k] * m[0] + cy[k] * m[1] + m[2]) < 32768.0 &&
+                        std::fabs(cx[k] * m[3] + cy[k] * m[4] + m[5]) < 32768.0,
+                    "augment_2d: matrices[%d] maps corner (%d, %d) beyond +-32768 (the range of PIL's fixed-point path)",
+                    b, cx[k], cy[k]);
+    HDF_CHECK_ARG(flips[b] <= 2, "augment_2d: flips[%d]=%d (0 none, 1 W, 2 H)", b, (int)flips[b]);
+  }
+  const size_t P = (size_t)H * W;
+  const size_t in_b[2] = {image_out ? (size_t)B * C * P * 4 : 0, (size_t)B * P};
+  const void* ins[2] = {image_out ? image : nullptr, (labels_out || onehot_out) ? labels : nullptr};
+  const size_t out_b[3] = {(size_t)B * C * P * 4, (size_t)B * P, (size_t)B * n_cls * P * 4};
+  const void* outs[3] = {image_out, labels_out, onehot_out};
+  for (int a = 0; a < 2; a++)
+    for (int o = 0; o < 3; o++)
+      HDF_CHECK_ARG(!overlaps(ins[a], in_b[a], outs[o], out_b[o]),
+                    "augment_2d: an output overlaps a source (the gather reads pixels other threads have written)");
+  if (!image_out) image = nullptr, C = 0;
+  for (int b0 = 0; b0 < B; b0 += AUG2D_CHUNK) {
+    const int nb = std::min(AUG2D_CHUNK, B - b0);
+    Aug2DChunk prm;
+    for (int k = 0; k < AUG2D_CHUNK; k++) {
+#pragma clang fp contract(off)
+      Aug2DSample& s = prm.s[k];
+      const double* m = matrices + 6 * (size_t)(b0 + std::min(k, nb - 1));   // the unused tail repeats the last sample
+      for (int j = 0; j < 6; j++) s.m[j] = m[j];
+      s.fx[0] = fix16(m[0]), s.fx[1] = fix16(m[1]), s.fx[2] = fix16(m[2] + m[0] * 0.5 + m[1] * 0.5);
+      s.fx[3] = fix16(m[3]), s.fx[4] = fix16(m[4]), s.fx[5] = fix16(m[5] + m[3] * 0.5 + m[4] * 0.5);
+      s.flip = flips[b0 + std::min(k, nb - 1)];
+      s.pad = 0;
+    }
+    const size_t o = (size_t)b0 * P;
+    const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64((int64_t)nb * (int64_t)P, 256), 2048);
+    hipLaunchKernelGGL(augment2d_kernel, dim3(gx), dim3(256), 0, st, image ? image + o * C : nullptr,
+                       labels ? labels + o : nullptr, nb, C, n_cls, H, W, prm, image_out ? image_out + o * C : nullptr,
+                       labels_out ? labels_out + o : nullptr, onehot_out ? onehot_out + o * n_cls : nullptr);
+    HDF_LAUNCH_CHECK();
+  }
   return HDF_OK;
 }
 

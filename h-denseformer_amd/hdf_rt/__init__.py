@@ -1,7 +1,8 @@
 """Runtime of the MI355X-native H-DenseFormer hot path (ctypes over libhdf_hip.so)."""
 from ._lib import BF16, F32, EXPORTS, HdfError, LIB_PATH, lib  # noqa: F401
 
-_AUGMENT = ("TrainTransform3D", "augment_3d", "crop_origin", "flip_flags", "trz_matrix")
+_AUGMENT = ("TrainTransform2D", "TrainTransform3D", "augment_2d", "augment_3d", "crop_origin", "flip2d_code", "flip_flags",
+            "rotate_degree", "rotate_matrix", "trz_matrix")
 _SURFACE = ("cal_score", "multi_dice", "multi_hd", "multi_jc", "multi_vs", "surface_scores")
 
 

@@ -302,6 +302,40 @@ int hdf_augment_3d(const float* image, const uint8_t* labels, int channels, int 
                    const double* affine, int flip_h, int flip_w, float* image_out, uint8_t* labels_out, float* onehot_out,
                    hdf_stream stream);
 
+/* ---- training augmentation of a 2-D batch on the device: RandomRotate2D, RandomFlip2D and To_Tensor
+ * (data_utils/transformer_2d.py:80-173, data_utils/data_loader.py:126-159), BIT FOR BIT what PIL computes (pinned to
+ * PIL 12.2.0: Image.rotate(angle, BILINEAR) on a mode-F plane, Image.rotate(angle, NEAREST) on a mode-L label).
+ * image [batch][channels][H][W] fp32 and labels [batch][H][W] uint8, both contiguous.  matrices: [batch][6] doubles on
+ * the HOST, m = (a, b, c, d, e, f) in the convention of PIL's Image.transform(AFFINE) (output pixel -> input
+ * coordinate); flips: [batch] bytes on the HOST, 0 none, 1 mirrors W, 2 mirrors H.  Both are read during the call.
+ * For output pixel (y, x) of a sample, first the flip: x -> W-1-x (1) or y -> H-1-y (2), i.e. the flip follows the
+ * rotation.  Then
+ *   image (PIL's affine_transform + bilinear_filter32F; fp64, every operation rounded, nothing fused):
+ *     xin = a*(x+0.5) + b*(y+0.5) + c,  yin = d*(x+0.5) + e*(y+0.5) + f, summed left to right.
+ *     xin < 0 || xin >= W || yin < 0 || yin >= H: the output is 0.0f.  Otherwise xin -= 0.5, yin -= 0.5,
+ *     x0 = floor(xin), y0 = floor(yin), dx = xin - x0, dy = yin - y0; on row clamp(y0, 0, H-1) the pixels p0, p1 of the
+ *     columns clamp(x0, 0, W-1), clamp(x0+1, 0, W-1): v1 = (double)p0 + (double)(float)(p1 - p0) * dx -- the neighbour
+ *     difference is an fp32 subtraction --; v2 the same on row y0+1 when 0 <= y0+1 < H, else v2 = v1;
+ *     out = (float)(v1 + (v2 - v1) * dy).
+ *   labels (PIL's affine_fixed, 16.16 fixed point): FIX(v) = (int64)floor(v*65536.0 + 0.5); a0 = FIX(a), a1 = FIX(b),
+ *     a3 = FIX(d), a4 = FIX(e), a2 = FIX(c + a*0.5 + b*0.5), a5 = FIX(f + d*0.5 + e*0.5);
+ *     xi = (a2 + y*a1 + x*a0) >> 16, yi = (a5 + y*a4 + x*a3) >> 16 (arithmetic shift; equal to PIL's running sums, the
+ *     integers being exact); labels_out = labels[yi][xi] when 0 <= xi < W && 0 <= yi < H, else 0.  The raw byte moves
+ *     unchanged.
+ *   one-hot of the moved byte by the rule of hdf_onehot_from_labels.
+ * Outputs, each written when non-null: image_out [batch][channels][H][W], labels_out [batch][H][W] uint8, onehot_out
+ * [batch][n_cls][H][W] fp32.  labels may be null only when both label outputs are null (image likewise when image_out
+ * is null).  No output may overlap a source.
+ * Refused with a message before any launch: a null or non-finite matrix; a matrix for which
+ * |x*a + y*b + c| < 32768 && |x*d + y*e + f| < 32768 fails at one of (0,0), (W,0), (0,H), (W,H) (PIL's check_fixed:
+ * past it PIL itself leaves the fixed-point path); flips[i] > 2; H or W outside 1..16384, channels outside 1..64, n_cls
+ * outside 2..8, batch < 1.
+ * ceil(batch / 32) launches (the per-sample parameters travel in the kernel arguments), no host synchronisation, no
+ * allocation. */
+int hdf_augment_2d(const float* image, const uint8_t* labels, int batch, int channels, int n_cls, int H, int W,
+                   const double* matrices, const uint8_t* flips, float* image_out, uint8_t* labels_out, float* onehot_out,
+                   hdf_stream stream);
+
 /* ---- optimizer: torch.optim.Adam as configured by trainer.py:793-840 (L2 weight decay on the mask) ---- */
 int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,

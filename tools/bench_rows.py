@@ -2,7 +2,8 @@
 bounded host-side restatement of what the reference does for the same call (numpy / torch CPU on this box's cores).
 
   python tools/bench_rows.py > profiles/<round>_rows.json      (one JSON object per line)
-  python tools/bench_rows.py augment                            (the augmentation row alone)
+  python tools/bench_rows.py augment                            (the 3-D augmentation row alone)
+  python tools/bench_rows.py augment2d                          (the 2-D training chain row alone)
 """
 import json
 import os
@@ -87,8 +88,65 @@ def augment_row(C=4, n_cls=4, S=128):
          cpu_baseline=cpu)
 
 
+def augment2d_row(B=24, C=2, n_cls=2, S=384):
+    """one TrainTransform2D call (clone, per-plane MRNormalize, one hdf_augment_2d launch) on the reference's 2-D batch,
+    24 x 2 x 384^2 (config.py:69-77), and its gather alone; next to the host chain it replaces, timed on this box:
+    MRNormalize + three PIL rotations per sample + flip + To_Tensor (transformer_2d.py, data_loader.py), one thread"""
+    from hdf_rt import TrainTransform2D, augment_2d, flip2d_code, rotate_degree, rotate_matrix
+    import random
+    gen = torch.Generator().manual_seed(12)
+    img = (torch.rand(B, C, S, S, generator=gen) * 900).to(DEV)
+    lab_h = torch.randint(0, n_cls, (B, S, S), generator=gen, dtype=torch.uint8)
+    lab = lab_h.to(DEV)
+    random.seed(12), np.random.seed(12)
+    tf = TrainTransform2D(n_cls)
+    us = 1e3 * gpu_ms(lambda: tf(img, lab), reps=30, warm=5)
+    us_val = 1e3 * gpu_ms(lambda: TrainTransform2D(n_cls, degrees=(), flip="")(img, lab), reps=30, warm=5)
+    mats = [rotate_matrix(rotate_degree(), S, S) for _ in range(B)]
+    codes = [flip2d_code() for _ in range(B)]
+    o_img, o_oh = torch.empty_like(img), torch.empty((B, n_cls, S, S), device=DEV)
+    us_k = 1e3 * gpu_ms(lambda: augment_2d(img, lab, n_cls, mats, codes, o_img, o_oh), reps=30, warm=5)
+    by = (4 * C + 1 + 4 * C + 4 * n_cls) * B * S * S
+    try:
+        from PIL import Image
+        img_np, lab_np = img.cpu().numpy(), lab_h.numpy()
+
+        def ref_chain():
+            for b in range(B):
+                x = img_np[b].copy()
+                for c in range(C):                                   # MRNormalize
+                    if x[c].max() != 0:
+                        x[c] = x[c] / x[c].max()
+                x[x < 0] = 0
+                deg = random.choice([-15, -10, -5, 0, 5, 10, 15])    # RandomRotate2D
+                x = np.asarray([np.array(Image.fromarray(ch).rotate(deg, Image.BILINEAR)).astype(np.float32) for ch in x])
+                y = np.array(Image.fromarray(lab_np[b]).rotate(deg, Image.NEAREST)).astype(np.float32)
+                u = np.random.uniform(0, 1)                          # RandomFlip2D
+                if u < 0.3:
+                    x, y = x[:, :, ::-1], y[:, ::-1]
+                elif u < 0.6:
+                    x, y = x[:, ::-1, :], y[::-1, :]
+                x, y = x.copy(), y.copy()
+                oh = np.empty((n_cls,) + y.shape, dtype=np.float32)  # To_Tensor
+                for z in range(1, n_cls):
+                    oh[z] = (y == z).astype(np.float32)
+                oh[0] = np.amax(oh[1:], axis=0) == 0
+
+        import PIL
+        cpu = {"kind": "port", "what": f"MRNormalize + {C + 1} PIL {PIL.__version__} rotations per sample + flip + To_Tensor, {B} samples",
+               "s_per_batch": cpu_s(ref_chain), "threads": 1}
+    except ImportError as exc:
+        cpu = {"kind": "not measured", "what": repr(exc)}
+    emit(row="TrainTransform2D", config=f"{B}x{C}x{S}^2 fp32 + uint8 labels, n_cls {n_cls}, normalize 'mr', 7 degrees, flip 'hv'",
+         gpu_us=us, validation_form_us=us_val, augment_2d_alone_us=us_k, algorithmic_bytes_gather=by,
+         achieved_GBps_gather=by / us_k / 1e3, hbm_peak_GBps=8000, cpu_baseline=cpu)
+
+
 if sys.argv[1:] == ["augment"]:
     augment_row()
+    sys.exit(0)
+if sys.argv[1:] == ["augment2d"]:
+    augment2d_row()
     sys.exit(0)
 
 g = torch.Generator().manual_seed(7)
@@ -150,6 +208,7 @@ emit(row="8f-3 mr_normalize_", config=f"{C}x{S}^3 fp32 in place (clone time {ms0
                    "threads": 1})
 
 augment_row()
+augment2d_row()
 
 # ---- 8f-2: sliding-window inference
 from models.HDenseFormer import HDenseFormer
