@@ -224,6 +224,31 @@ int hdf_augment_2d(const float* image, const uint8_t* labels, int batch, int cha
   return hdf_launch_augment2d(image, labels, batch, channels, n_cls, H, W, matrices, flips, image_out, labels_out,
                               onehot_out, (hipStream_t)stream);
 }
+int64_t hdf_label_bbox_workspace_bytes(int batch) { return (int64_t)hdf_label_bbox_ws_bytes(batch); }
+int hdf_label_bbox_2d(const uint8_t* labels, int batch, int H, int W, int32_t* bbox, void* workspace,
+                      int64_t workspace_bytes, hdf_stream stream) {
+  HDF_CHECK_ARG(labels && bbox && workspace, "label_bbox_2d: null argument");
+  HDF_CHECK_ARG(workspace_bytes >= (int64_t)hdf_label_bbox_ws_bytes(batch),
+                "label_bbox_2d: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+                (long long)hdf_label_bbox_ws_bytes(batch));
+  return hdf_launch_label_bbox2d(labels, batch, H, W, bbox, workspace, (hipStream_t)stream);
+}
+int hdf_zoom_2d(const float* image, const uint8_t* labels, int batch, int channels, int H, int W, const int32_t* keep,
+                const int32_t* canvas, float* image_out, uint8_t* labels_out, hdf_stream stream) {
+  HDF_CHECK_ARG(keep, "zoom_2d: null keep");
+  HDF_CHECK_ARG(canvas, "zoom_2d: null canvas");
+  // both host arrays are copied into the kernel arguments chunk by chunk: the caller may reuse them at once
+  return hdf_launch_zoom2d(image, labels, batch, channels, H, W, keep, canvas, image_out, labels_out,
+                           (hipStream_t)stream);
+}
+int hdf_intensity_2d(float* image, int batch, int channels, int H, int W, const double* gamma, const uint8_t* noise,
+                     uint64_t seed, float low_clip, hdf_stream stream) {
+  HDF_CHECK_ARG(image && gamma && noise, "intensity_2d: null argument");
+  HDF_CHECK_ARG(H >= 1 && W >= 1 && H <= 16384 && W <= 16384, "intensity_2d: plane %dx%d (1..16384 a side)", H, W);
+  HDF_CHECK_ARG(channels >= 1 && channels <= 64, "intensity_2d: channels=%d (1..64)", channels);
+  return hdf_launch_intensity2d(image, batch, (int64_t)channels * H * W, gamma, noise, seed, low_clip,
+                                (hipStream_t)stream);
+}
 int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   float grad_scale, hdf_stream stream) {

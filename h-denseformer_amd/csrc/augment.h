@@ -1,4 +1,5 @@
-// The device-side input pipeline (augment.hip): normalisation, one-hot staging, the 3-D and 2-D training augmentation.
+// The device-side input pipeline (augment.hip): normalisation, one-hot staging, the 3-D and 2-D training augmentation
+// (rotation + flip + one-hot; label bounding box; erase + zoom; gamma + noise).
 #pragma once
 #include "hdf_common.h"
 
@@ -31,6 +32,34 @@ struct Aug2DChunk {
 int hdf_launch_augment2d(const float* image, const uint8_t* labels, int B, int C, int n_cls, int H, int W,
                          const double* matrices, const uint8_t* flips, float* image_out, uint8_t* labels_out,
                          float* onehot_out, hipStream_t st);
+
+// the parameters of one sample of the 2-D zoom: the keep-rectangle of the erase, rows [r0, r1) x columns [c0, c1), and the
+// canvas, sw wide and sh high with the plane's origin at (oy, ox); a chunk of them is one kernel argument, passed by value
+struct Zoom2DSample {
+  int r0, r1, c0, c1, sw, sh, ox, oy;
+};
+struct Zoom2DChunk {
+  Zoom2DSample s[AUG2D_CHUNK];
+};
+
+// a batch through RandomErase2D + RandomZoom2D, bit-exact to PIL's crop / expand + resize: image [B][C][H][W] fp32,
+// labels [B][H][W] uint8, keep [B][4] and canvas [B][4] int32 on the HOST (read during the call); ceil(B / AUG2D_CHUNK)
+// launches.  data_utils/transformer_2d.py:11-77, 177-275
+int hdf_launch_zoom2d(const float* image, const uint8_t* labels, int B, int C, int H, int W, const int32_t* keep,
+                      const int32_t* canvas, float* image_out, uint8_t* labels_out, hipStream_t st);
+
+// (non-zero count, rmin, rmax, cmin, cmax) of each class map of labels [B][H][W] into bbox [B][5] int32 on the device
+size_t hdf_label_bbox_ws_bytes(int B);
+int hdf_launch_label_bbox2d(const uint8_t* labels, int B, int H, int W, int32_t* bbox, void* ws, hipStream_t st);
+
+// RandomAdjust2D + RandomNoise2D in place on image [B][n] fp32: gamma [B] doubles and noise [B] bytes on the HOST
+// (read during the call); ceil(B / AUG2D_CHUNK) launches.  data_utils/transformer_2d.py:279-322
+struct Intensity2DChunk {
+  double gamma[AUG2D_CHUNK];
+  uint8_t noise[AUG2D_CHUNK];
+};
+int hdf_launch_intensity2d(float* image, int B, int64_t n, const double* gamma, const uint8_t* noise, uint64_t seed,
+                           float low_clip, hipStream_t st);
 
 // in-place input normalisation of one sample [C][V] fp32 (data_utils/data_loader.py:39-68); mode 0 MR, 1 PET/CT
 size_t hdf_norm_ws_bytes(int C);

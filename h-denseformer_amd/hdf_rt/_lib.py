@@ -71,6 +71,10 @@ _PROTOS = {
     "hdf_onehot_from_labels": (_i, [_vp, _vp, _i, _i, _i64, _vp]),
     "hdf_augment_3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _pd, _i, _i, _vp, _vp, _vp, _vp]),
     "hdf_augment_2d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _pd, _vp, _vp, _vp, _vp, _vp]),
+    "hdf_label_bbox_workspace_bytes": (_i64, [_i]),
+    "hdf_label_bbox_2d": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "hdf_zoom_2d": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "hdf_intensity_2d": (_i, [_vp, _i, _i, _i, _i, _pd, _vp, _u64, _f, _vp]),
     "hdf_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _vp]),
     "hdf_optim_step": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp, _vp]),
     "hdf_op_to_channels_last": (_i, [_i, _vp, _vp, _i, _i, _i, _i64, _vp]),

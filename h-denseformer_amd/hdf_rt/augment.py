@@ -7,7 +7,13 @@ np.random / random reproduces its parameters.  No CPU fallback.
 The default 2-D chain (trainer.py:152-172 with config.py's transform_2d = [1,6,7,10]): MRNormalize per plane, then
 RandomRotate2D + RandomFlip2D + To_Tensor ONE gather kernel per batch (hdf_augment_2d), bit for bit what PIL computes
 on the host (pinned to PIL 12.2.0; include/hdf.h).  The matrix is built here, in Python, because PIL rounds the cosine
-and the sine with Python's decimal round(., 15)."""
+and the sine with Python's decimal round(., 15).
+
+The rest of the 2-D list (trainer.py:152-168): RandomErase2D (3) and RandomZoom2D (4) are one gather launch before the
+rotation (hdf_zoom_2d, bit for bit PIL's crop / ImageOps.expand + resize), fed by one label bounding-box reduction per
+batch (hdf_label_bbox_2d); RandomAdjust2D (8) and RandomNoise2D (9) one in-place launch after it (hdf_intensity_2d).
+TrainTransform2D.from_ids maps the reference's ids; CropResize (2), RandomDistort2D (5) and Trunc_and_Normalize (11) are
+refused by name."""
 import ctypes as C
 import math
 import random
@@ -211,20 +217,222 @@ def augment_2d(image, labels, n_cls, matrices, flips, out_image=None, out_onehot
     return out_image, out_onehot
 
 
+# --------------------------------------------------------------------------------- erase, zoom, gamma, noise (2-D)
+def erase2d_keep(bbox_row, H, W, window=(64, 64), rng=random):
+    """The keep-rectangle (r0, r1, c0, c1) of RandomErase2D(scale_flag=False) (data_utils/transformer_2d.py:32-73) for a
+    sample whose label bounding box is bbox_row = (nonzero_count, rmin, rmax, cmin, cmax), drawing from `rng` in the
+    reference's order.  Non-empty label: the window is the box grown by half of `window`, clamped to the plane, no draw;
+    empty label: four rng.randint, (0, 64), (-64, 0) for the rows, then the same for the columns (the reference's
+    literals).  Then rng.choice of the direction: 't' zeroes rows [:rw0[0]], 'd' rows [rw0[1]:], 'l' columns [:rw1[0]],
+    'r' columns [rw1[1]:], 'no_erase' nothing -- with Python's slice rules, so a drawn 0 for 'd' or 'r' erases the whole
+    plane and a negative value counts from the end."""
+    n, rmin, rmax, cmin, cmax = (int(v) for v in bbox_row)
+    max_h, max_w = window
+    if n != 0:
+        rw0 = (max(rmin - max_h // 2, 0), min(rmax + max_h // 2, H))
+        rw1 = (max(cmin - max_w // 2, 0), min(cmax + max_w // 2, W))
+    else:
+        rw0 = (rng.randint(0, 64), rng.randint(-64, 0))
+        rw1 = (rng.randint(0, 64), rng.randint(-64, 0))
+    direction = rng.choice(['t', 'd', 'l', 'r', 'no_erase'])
+    r0, r1, c0, c1 = 0, H, 0, W
+    if direction == 't':
+        r0 = slice(None, rw0[0]).indices(H)[1]
+    elif direction == 'd':
+        r1 = slice(rw0[1], None).indices(H)[0]
+    elif direction == 'l':
+        c0 = slice(None, rw1[0]).indices(W)[1]
+    elif direction == 'r':
+        c1 = slice(rw1[1], None).indices(W)[0]
+    return (r0, r1, c0, c1)
+
+
+def zoom2d_canvas(bbox_row, H, W, scale=(0.8, 1.2), rng=random):
+    """The canvas (sw, sh, ox, oy) of RandomZoom2D (data_utils/transformer_2d.py:207-259) for hdf_zoom_2d, drawing from
+    `rng` in the reference's order: s = rng.uniform(*scale), tw = int(W * s), th = int(H * s).
+    s < 1, a crop at (x1, y1): an empty label draws x1 = randint(0, W - th), y1 = randint(0, H - tw) -- the reference
+    reads PIL's (width, height) as (h, w), so th bounds the column and tw the row; the swap is kept.  A non-empty one,
+    with xl = max(0, rmin), xr = min(H, rmax), yl = max(0, cmin), yr = min(W, cmax): x1 = randint(max(0, min(yl, yr -
+    th)), min(yl, W - th)), then y1 = randint(max(0, min(xl, xr - tw)), min(xl, H - tw)).  An empty range raises
+    ValueError, as random.randint does in the reference.  The canvas is (tw, th, -x1, -y1).
+    s >= 1, a pad: p0 = int(rng.uniform(0, (tw - H) / 2)), p1 = int(rng.uniform(0, (th - W) / 2)), then
+    ImageOps.expand(border=(p0, p1, tw - H, th - W)) -- the same swap: the reference's `tw - w` and `th - h` subtract the
+    height from the padded width and the width from the padded height.  The canvas is (p0 + W + tw - H, p1 + H + th - W,
+    p0, p1); on a square plane, the reference's own case, that is (tw + p0, th + p1, p0, p1) with p0 below (tw - W) / 2."""
+    n, rmin, rmax, cmin, cmax = (int(v) for v in bbox_row)
+    s = rng.uniform(scale[0], scale[1])
+    tw, th = int(W * s), int(H * s)
+    if s < 1.:
+        if n == 0:
+            cols, rows = (0, W - th), (0, H - tw)
+        else:
+            xl, xr, yl, yr = max(0, rmin), min(H, rmax), max(0, cmin), min(W, cmax)
+            rows = (max(0, min(xl, xr - tw)), min(xl, H - tw))
+            cols = (max(0, min(yl, yr - th)), min(yl, W - th))
+        x1 = rng.randint(cols[0], cols[1])
+        y1 = rng.randint(rows[0], rows[1])
+        return (tw, th, -x1, -y1)
+    p0 = int(rng.uniform(0, (tw - H) / 2))
+    p1 = int(rng.uniform(0, (th - W) / 2))
+    return (p0 + W + tw - H, p1 + H + th - W, p0, p1)
+
+
+def gamma2d(scale=(0.8, 1.2), rng=random):
+    """The gamma of RandomAdjust2D (data_utils/transformer_2d.py:297): one rng.uniform."""
+    return rng.uniform(scale[0], scale[1])
+
+
+def noise2d_flag(rng=random):
+    """RandomNoise2D (data_utils/transformer_2d.py:317-318): one rng.uniform(0, 1); the noise is on above 0.9."""
+    return rng.uniform(0, 1) > 0.9
+
+
+def _device_batch(image, what):
+    if not torch.is_tensor(image) or image.device.type != "cuda":
+        raise _lib.HdfError(f"{what} needs device tensors (there is no CPU path)")
+
+
+def _int_rows(rows, b, what):
+    a = np.asarray(rows)
+    if a.shape != (b, 4) or a.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be ({b}, 4) integers, got {rows!r}")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def label_bbox_2d(labels):
+    """(nonzero_count, rmin, rmax, cmin, cmax) of every class map of a uint8 device batch [B, H, W] as an int32 device
+    tensor [B, 5]; (0, H, -1, W, -1) for an empty one.  Semantics: include/hdf.h, hdf_label_bbox_2d."""
+    _device_batch(labels, "label_bbox_2d")
+    if labels.dtype != torch.uint8 or labels.dim() != 3:
+        raise ValueError(f"labels must be a uint8 tensor [B, H, W], got {labels.dtype} {tuple(labels.shape)}")
+    labels = labels.contiguous()
+    b, h, w = (int(s) for s in labels.shape)
+    nbytes = int(lib().hdf_label_bbox_workspace_bytes(b))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=labels.device)
+    out = torch.empty((b, 5), dtype=torch.int32, device=labels.device)
+    check(lib().hdf_label_bbox_2d(ptr(labels), b, h, w, ptr(out), ptr(ws), nbytes, stream_ptr()), "hdf_label_bbox_2d")
+    return out
+
+
+def zoom_2d(image, labels, keeps, canvases, out_image=None, out_labels=None):
+    """Erase + crop or pad + resample of a batch in one launch per 32 samples.  image: fp32 device tensor [B, C, H, W];
+    labels: uint8 device tensor [B, H, W] (None: image only); keeps: [B][4] from erase2d_keep ((0, H, 0, W) erases
+    nothing); canvases: [B][4] from zoom2d_canvas ((W, H, 0, 0) zooms nothing).  Returns (image, labels): new tensors, or
+    out_image / out_labels when given.  Semantics: include/hdf.h, hdf_zoom_2d."""
+    _device_batch(image, "zoom_2d")
+    if image.dtype != torch.float32 or image.dim() != 4:
+        raise ValueError(f"image must be a float32 tensor [B, C, H, W], got {image.dtype} {tuple(image.shape)}")
+    image = image.contiguous()
+    b, c, h, w = (int(s) for s in image.shape)
+    if labels is not None:
+        if (not torch.is_tensor(labels) or labels.device != image.device or labels.dtype != torch.uint8
+                or tuple(labels.shape) != (b, h, w)):
+            raise ValueError(f"labels must be a uint8 tensor {(b, h, w)} on {image.device}")
+        labels = labels.contiguous()
+    keep, canvas = _int_rows(keeps, b, "keeps"), _int_rows(canvases, b, "canvases")
+
+    def out(t, shape, dtype, what):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=image.device)
+        if (not torch.is_tensor(t) or t.device != image.device or t.dtype != dtype or tuple(t.shape) != shape
+                or not t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor {shape} on {image.device}")
+        return t
+
+    out_image = out(out_image, (b, c, h, w), torch.float32, "out_image")
+    if labels is None:
+        if out_labels is not None:
+            raise ValueError("a label output needs labels")
+    else:
+        out_labels = out(out_labels, (b, h, w), torch.uint8, "out_labels")
+    check(lib().hdf_zoom_2d(ptr(image), ptr(labels), b, c, h, w, keep.ctypes.data, canvas.ctypes.data, ptr(out_image),
+                            ptr(out_labels), stream_ptr()), "hdf_zoom_2d")
+    return out_image, out_labels
+
+
+def intensity_2d_(image, gammas, noise, seed=0, low_clip=0.0):
+    """Gamma and Gaussian noise in place on an fp32 device batch [B, C, H, W], one launch per 32 samples.  gammas: [B]
+    from gamma2d (1.0 leaves a sample alone); noise: [B] flags from noise2d_flag; seed: the 64-bit key of the noise
+    field; low_clip: 0 for an image without negatives (after MRNormalize), -1 otherwise, as skimage chooses.  Returns
+    image.  Semantics: include/hdf.h, hdf_intensity_2d."""
+    _device_batch(image, "intensity_2d_")
+    if image.dtype != torch.float32 or image.dim() != 4 or not image.is_contiguous():
+        raise ValueError(f"image must be a contiguous float32 tensor [B, C, H, W], got {image.dtype} "
+                         f"{tuple(image.shape)}")
+    b, c, h, w = (int(s) for s in image.shape)
+    g = np.ascontiguousarray(gammas, dtype=np.float64)
+    flags = np.ascontiguousarray(np.asarray(noise), dtype=np.uint8)
+    if g.shape != (b,) or flags.shape != (b,):
+        raise ValueError(f"gammas and noise must hold {b} values each, got {g.shape} and {flags.shape}")
+    check(lib().hdf_intensity_2d(ptr(image), b, c, h, w, g.ctypes.data_as(C.POINTER(C.c_double)), flags.ctypes.data,
+                                 int(seed) & (2 ** 64 - 1), float(low_clip), stream_ptr()), "hdf_intensity_2d")
+    return image
+
+
+# the reference's transform_list_2d (trainer.py:152-168) by id
+TRANSFORM_2D_NAMES = {1: "MRNormalize", 2: "CropResize", 3: "RandomErase2D", 4: "RandomZoom2D", 5: "RandomDistort2D",
+                      6: "RandomRotate2D", 7: "RandomFlip2D", 8: "RandomAdjust2D", 9: "RandomNoise2D", 10: "To_Tensor",
+                      11: "Trunc_and_Normalize"}
+_REFUSED_2D = {2: "it needs skimage's anti-aliased resize, for which no exact contract is pinned",
+               5: "it is OpenCV's GaussianBlur + resize + fixed-point remap, for which no exact contract is pinned",
+               11: "it is not part of the device chain"}
+
+
 class TrainTransform2D:
     """transform_2d = [1,6,7,10] of trainer.py:152-172 on a device batch: MRNormalize (normalize='mr') ->
     RandomRotate2D(degrees) -> RandomFlip2D(flip) -> To_Tensor.  degrees=() and flip='' give the validation chain
-    (trainer.py:173-176: normalise, one-hot).  MRNormalize works per plane, so a batch is simply more channels."""
+    (trainer.py:173-176: normalise, one-hot).  MRNormalize works per plane, so a batch is simply more channels.
 
-    def __init__(self, n_cls, normalize="mr", degrees=REFERENCE_DEGREES, flip="hv"):
+    The other entries of the list are off unless asked for: erase=(64, 64) is RandomErase2D(scale_flag=False) with that
+    window, zoom=(0.8, 1.2) RandomZoom2D, gamma=(0.8, 1.2) RandomAdjust2D, noise=True RandomNoise2D; from_ids maps the
+    reference's ids.  The order is the list's: normalise, erase, zoom, rotate, flip, gamma, noise, one-hot.  Erase, zoom,
+    rotation and flip are exact to the reference's PIL calls; the gamma is pow in fp64 rounded once (the reference's is
+    numpy's fp32 power); the noise is statistical: N(0, 0.01) from a counter-based generator keyed by ONE
+    np.random.randint per batch, where the reference draws C*H*W normals per noisy sample from np.random -- the one
+    place where the np.random stream leaves the reference's.  Noise needs normalize='mr': skimage clips at 0 when the
+    image holds no negative, which MRNormalize guarantees without a reduction."""
+
+    def __init__(self, n_cls, normalize="mr", degrees=REFERENCE_DEGREES, flip="hv", erase=None, zoom=None, gamma=None,
+                 noise=False):
         if normalize not in (None, "mr"):
             raise ValueError(f"normalize must be None or 'mr', got {normalize!r}")
+        if noise and normalize != "mr":
+            raise ValueError("noise needs normalize='mr': its lower clip is 0 only for an image without negatives")
+        for name, pair in (("erase", erase), ("zoom", zoom), ("gamma", gamma)):
+            if pair is not None and (not isinstance(pair, tuple) or len(pair) != 2):
+                raise ValueError(f"{name} must be None or a pair, got {pair!r}")
         self.n_cls, self.normalize, self.degrees, self.flip = n_cls, normalize, tuple(degrees), flip
+        self.erase, self.zoom, self.gamma, self.noise = erase, zoom, gamma, bool(noise)
+
+    @classmethod
+    def from_ids(cls, n_cls, transform_2d, train=True):
+        """The chain the reference builds from config.py's transform_2d (trainer.py:152-176): ids into its list, in
+        ascending order as every configuration of the reference has them.  train=False keeps MRNormalize (1) and
+        To_Tensor (10) only.  CropResize (2), RandomDistort2D (5) and Trunc_and_Normalize (11) raise ValueError by
+        name; To_Tensor (10) must be present, the chain ends in the one-hot."""
+        ids = [int(i) for i in transform_2d]
+        for i in ids:
+            if i not in TRANSFORM_2D_NAMES:
+                raise ValueError(f"transform_2d id {i} is not in the reference's list (1..11)")
+            if i in _REFUSED_2D:
+                raise ValueError(f"transform_2d id {i} ({TRANSFORM_2D_NAMES[i]}) does not run on the device: "
+                                 f"{_REFUSED_2D[i]}")
+        if ids != sorted(set(ids)):
+            raise ValueError(f"transform_2d must list each id once, in ascending order, got {ids}")
+        if 10 not in ids:
+            raise ValueError("transform_2d must hold 10 (To_Tensor): the chain returns the one-hot")
+        if not train:
+            ids = [i for i in ids if i in (1, 10)]
+        return cls(n_cls, normalize="mr" if 1 in ids else None, degrees=REFERENCE_DEGREES if 6 in ids else (),
+                   flip="hv" if 7 in ids else "", erase=(64, 64) if 3 in ids else None,
+                   zoom=(0.8, 1.2) if 4 in ids else None, gamma=(0.8, 1.2) if 8 in ids else None, noise=9 in ids)
 
     def __call__(self, image, labels):
         """image: raw fp32 [B, C, H, W], labels: uint8 [B, H, W], both on the device.  Returns (image [B, C, H, W],
-        onehot [B, n_cls, H, W]); the arguments are left untouched.  Per sample the degree is drawn first (random),
-        the flip second (np.random), as the reference's chain does."""
+        onehot [B, n_cls, H, W]); the arguments are left untouched.  Per sample the draws follow the chain: erase and
+        zoom (random), the degree (random), the flip (np.random), the gamma and the noise flag (random); after the
+        batch, one np.random.randint for the noise seed when noise is on.  With erase or zoom on, the labels' bounding
+        boxes come to the host in one copy before the draws (the only synchronisation of the call)."""
         if not torch.is_tensor(image) or image.device.type != "cuda":
             raise _lib.HdfError("TrainTransform2D needs device tensors (there is no CPU path)")
         if image.dim() != 4:
@@ -236,10 +444,33 @@ class TrainTransform2D:
             planes = image.view(b * c, 1, h, w)
             for k in range(0, b * c, 64):                              # the channel cap of hdf_normalize_mr
                 mr_normalize_(planes[k:k + 64])
-        if not self.degrees and not self.flip:
+        moves = self.erase is not None or self.zoom is not None
+        shades = self.gamma is not None or self.noise
+        if not self.degrees and not self.flip and not moves and not shades:
             return image, onehot_from_labels(labels, self.n_cls)
-        mats, codes = [], []
-        for _ in range(b):
-            mats.append(rotate_matrix(rotate_degree(self.degrees) if self.degrees else 0, w, h))
-            codes.append(flip2d_code(self.flip))
-        return augment_2d(image, labels, self.n_cls, mats, codes)
+        d = self.draw(b, h, w, label_bbox_2d(labels).cpu().numpy() if moves else None)
+        if moves:
+            image, labels = zoom_2d(image, labels, d["keeps"], d["canvases"])
+        out_image, onehot = augment_2d(image, labels, self.n_cls, d["matrices"], d["flips"])
+        if shades:
+            intensity_2d_(out_image, d["gammas"], d["noise"], d["seed"], 0.0)
+        return out_image, onehot
+
+    def draw(self, batch, h, w, bbox=None):
+        """The random parameters of one batch of `batch` h x w samples, drawn in the reference's order and nothing else:
+        per sample erase and zoom (random; bbox [batch][5] from label_bbox_2d, needed when either is on), the degree
+        (random), the flip (np.random), the gamma and the noise flag (random); then one np.random.randint for the noise
+        seed when noise is on.  A transform that is off draws nothing and gives its neutral parameter.  Returns a dict:
+        keeps, canvases, matrices, flips, gammas, noise (lists of `batch`) and seed."""
+        if (self.erase is not None or self.zoom is not None) and bbox is None:
+            raise ValueError("erase and zoom need the labels' bounding boxes")
+        d = {k: [] for k in ("keeps", "canvases", "matrices", "flips", "gammas", "noise")}
+        for k in range(batch):
+            d["keeps"].append(erase2d_keep(bbox[k], h, w, self.erase) if self.erase is not None else (0, h, 0, w))
+            d["canvases"].append(zoom2d_canvas(bbox[k], h, w, self.zoom) if self.zoom is not None else (w, h, 0, 0))
+            d["matrices"].append(rotate_matrix(rotate_degree(self.degrees) if self.degrees else 0, w, h))
+            d["flips"].append(flip2d_code(self.flip))
+            d["gammas"].append(gamma2d(self.gamma) if self.gamma is not None else 1.0)
+            d["noise"].append(int(noise2d_flag()) if self.noise else 0)
+        d["seed"] = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) if self.noise else 0
+        return d

@@ -336,6 +336,69 @@ int hdf_augment_2d(const float* image, const uint8_t* labels, int batch, int cha
                    const double* matrices, const uint8_t* flips, float* image_out, uint8_t* labels_out, float* onehot_out,
                    hdf_stream stream);
 
+/* ---- the rest of the reference's 2-D transform list on the device: RandomErase2D (3), RandomZoom2D (4),
+ * RandomAdjust2D (8) and RandomNoise2D (9) of trainer.py:152-168 (data_utils/transformer_2d.py).  They run before
+ * (erase, zoom) and after (gamma, noise) hdf_augment_2d, which still makes the one-hot.
+ *
+ * hdf_label_bbox_2d: labels [batch][H][W] uint8 on the device -> bbox [batch][5] int32 on the device,
+ * (nonzero_count, rmin, rmax, cmin, cmax) of the non-zero bytes of each sample; a sample without one gives
+ * (0, H, -1, W, -1).  RandomErase2D and RandomZoom2D both branch on it before they draw.  Two launches for the batch, no
+ * host synchronisation, no allocation; workspace: hdf_label_bbox_workspace_bytes(batch) bytes.  H and W 1..16384,
+ * batch 1..65535. */
+int64_t hdf_label_bbox_workspace_bytes(int batch);
+int hdf_label_bbox_2d(const uint8_t* labels, int batch, int H, int W, int32_t* bbox, void* workspace,
+                      int64_t workspace_bytes, hdf_stream stream);
+
+/* hdf_zoom_2d: erase, crop or pad, and resample a batch in one gather launch per 32 samples, BIT FOR BIT what PIL 12.2.0
+ * computes: resize((W, H), BILINEAR) of the mode-F canvas per image plane, resize((W, H), NEAREST) of the mode-L canvas
+ * of the class map.  image [batch][channels][H][W] fp32 and labels [batch][H][W] uint8, both contiguous.  On the HOST,
+ * read during the call, per sample:
+ *   keep [batch][4] int32 = (r0, r1, c0, c1): source pixels of the IMAGE outside rows [r0, r1) or columns [c0, c1) read
+ *     as 0.0f (RandomErase2D; the labels are not touched).  (0, H, 0, W) erases nothing, r0 == r1 everything.
+ *   canvas [batch][4] int32 = (sw, sh, ox, oy): the canvas is sw wide and sh high; its pixel (cy, cx) is the source
+ *     pixel (cy - oy, cx - ox) when that lies inside the plane, else 0.  PIL's crop((x1, y1, x1+tw, y1+th)) is
+ *     (tw, th, -x1, -y1); ImageOps.expand(border=(p0, p1, tw-W, th-H), fill=0) is (tw+p0, th+p1, p0, p1).
+ * image (ImagingResample: two separable passes, horizontal then vertical, fp64, every operation rounded, nothing
+ *   fused).  One axis with input size n_in (sw or sh) and output size n_out, output index xx:
+ *     scale = (double)n_in / n_out, fs = max(scale, 1.0), support = fs, ss = 1.0 / fs,
+ *     center = (xx + 0.5) * scale,
+ *     xmin = (int)(center - support + 0.5) clamped below at 0, xmax = (int)(center + support + 0.5) clamped above at n_in,
+ *     for x in [0, xmax - xmin): t = (x + xmin - center + 0.5) * ss, w[x] = 1 - |t| if |t| < 1 else 0,
+ *     ww = sum of w left to right, k[x] = w[x] / ww when ww != 0,
+ *     out = (float)(sum of (double)pixel[xmin + x] * k[x], left to right from 0.0).
+ *   The horizontal result is rounded to fp32 before the vertical pass reads it.  A pass whose n_in == n_out is skipped:
+ *   the value passes through unchanged (so a canvas of (W, H, 0, 0) copies the erased plane, -0.0 included).
+ * labels (ImagingScaleAffine, nearest): per axis a0 = (double)n_in / n_out and a RUNNING sum xo = a0 * 0.5; for each
+ *   output index in order src = (int)xo, then xo += a0 -- the roundings of the running sum are part of the contract,
+ *   (int)((x + 0.5) * a0) differs at some sizes.  labels_out = canvas[src_y][src_x]; the raw byte moves unchanged.
+ * Outputs, each written when non-null: image_out [batch][channels][H][W], labels_out [batch][H][W].  labels may be null
+ * when labels_out is (image likewise).  No output may overlap a source or the other output.
+ * Refused with a message before any launch: null keep or canvas, no output, an output without its source, overlapping
+ * buffers; sw outside [ceil(W/4), 4W] or sh outside [ceil(H/4), 4H]; |ox| or |oy| above 65536; a keep-rectangle that is
+ * not 0 <= r0 <= r1 <= H, 0 <= c0 <= c1 <= W; H or W outside 1..16384, channels outside 1..64, batch < 1.
+ * ceil(batch / 32) launches (the per-sample parameters travel in the kernel arguments), no host synchronisation, no
+ * allocation. */
+int hdf_zoom_2d(const float* image, const uint8_t* labels, int batch, int channels, int H, int W, const int32_t* keep,
+                const int32_t* canvas, float* image_out, uint8_t* labels_out, hdf_stream stream);
+
+/* hdf_intensity_2d: gamma and Gaussian noise in place on image [batch][channels][H][W] fp32, one launch per 32 samples.
+ * On the HOST, read during the call: gamma [batch] doubles (1.0 leaves the sample alone) and noise [batch] bytes, 0 or 1.
+ * gamma (skimage's adjust_gamma on a float image, (image / 1.0) ** gamma * 1.0): x > 0 -> (float)pow((double)x,
+ *   (double)(float)gamma), one rounding; x <= 0 -> 0 (skimage raises on negative input; MRNormalize leaves none).  A
+ *   gamma that rounds to 1.0f leaves the bits alone.
+ * noise, after the gamma (skimage's random_noise(mode='gaussian'), mean 0, var 0.01): out = (float)clip((double)x +
+ *   0.1 * z, low_clip, 1.0), z ~ N(0, 1).  skimage takes low_clip = -1 when the image holds a negative, else 0; the
+ *   caller says which.  z = sqrt(-2 ln u1) * cos(2 pi u2) in fp64 from Philox-4x32-10 with the key (seed low word, seed
+ *   high word) on the counter (e low word, e high word, sample, 0), e the element's index within its sample:
+ *   u1 = ((w0 << 20 | w1 >> 12) + 0.5) * 2^-52, u2 = (w2 + 0.5) * 2^-32.  z is a pure function of (seed, sample, e): no
+ *   generator state lives on the device and nothing depends on the launch geometry.  The field is statistical, not the
+ *   reference's np.random stream.
+ * Refused before any launch: a null argument, a gamma that is negative or not finite, noise[i] > 1, a low_clip that is
+ * not finite or above 1, H or W outside 1..16384, channels outside 1..64, batch < 1.  No host synchronisation, no
+ * allocation. */
+int hdf_intensity_2d(float* image, int batch, int channels, int H, int W, const double* gamma, const uint8_t* noise,
+                     uint64_t seed, float low_clip, hdf_stream stream);
+
 /* ---- optimizer: torch.optim.Adam as configured by trainer.py:793-840 (L2 weight decay on the mask) ---- */
 int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,

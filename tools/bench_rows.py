@@ -4,6 +4,7 @@ bounded host-side restatement of what the reference does for the same call (nump
   python tools/bench_rows.py > profiles/<round>_rows.json      (one JSON object per line)
   python tools/bench_rows.py augment                            (the 3-D augmentation row alone)
   python tools/bench_rows.py augment2d                          (the 2-D training chain row alone)
+  python tools/bench_rows.py transforms2d                       (the full 2-D transform list row alone)
 """
 import json
 import os
@@ -142,11 +143,50 @@ def augment2d_row(B=24, C=2, n_cls=2, S=384):
          achieved_GBps_gather=by / us_k / 1e3, hbm_peak_GBps=8000, cpu_baseline=cpu)
 
 
+def transforms2d_row(B=24, C=3, n_cls=2, S=384):
+    """one TrainTransform2D.from_ids(n_cls, [1,3,4,6,7,8,9,10]) call -- clone, MRNormalize, the label bounding boxes and
+    their copy to the host, hdf_zoom_2d, hdf_augment_2d, hdf_intensity_2d -- on 24 x 3 x 384^2, and its new parts alone:
+    the bounding-box reduction, the erase + zoom gather with a zoom on every sample, gamma + noise with BOTH on every
+    sample (the chain draws noise for one sample in ten).  Same protocol as augment2d_row."""
+    from hdf_rt import (TrainTransform2D, erase2d_keep, gamma2d, intensity_2d_, label_bbox_2d, zoom2d_canvas, zoom_2d)
+    import random
+    gen = torch.Generator().manual_seed(13)
+    img = (torch.rand(B, C, S, S, generator=gen) * 900).to(DEV)
+    lab_h = torch.zeros((B, S, S), dtype=torch.uint8)
+    for b in range(0, B, 2):                                         # every other sample carries a lesion-sized box
+        r, c = 40 + 11 * b, 300 - 9 * b
+        lab_h[b, r:r + 30, c:c + 24] = 1
+    lab = lab_h.to(DEV)
+    random.seed(13), np.random.seed(13)
+    tf = TrainTransform2D.from_ids(n_cls, [1, 3, 4, 6, 7, 8, 9, 10])
+    us = 1e3 * gpu_ms(lambda: tf(img, lab), reps=30, warm=5)
+    us_default = 1e3 * gpu_ms(lambda: TrainTransform2D(n_cls)(img, lab), reps=30, warm=5)
+    us_bbox = 1e3 * gpu_ms(lambda: label_bbox_2d(lab), reps=30, warm=5)
+    bbox = label_bbox_2d(lab).cpu().numpy()
+    keeps = [erase2d_keep(bbox[b], S, S) for b in range(B)]
+    canvases = [zoom2d_canvas(bbox[b], S, S) for b in range(B)]
+    norm = torch.rand(B, C, S, S, generator=gen).to(DEV)
+    o_img, o_lab = torch.empty_like(norm), torch.empty_like(lab)
+    us_zoom = 1e3 * gpu_ms(lambda: zoom_2d(norm, lab, keeps, canvases, o_img, o_lab), reps=30, warm=5)
+    gammas = [gamma2d() for _ in range(B)]
+    us_int = 1e3 * gpu_ms(lambda: intensity_2d_(o_img, gammas, [1] * B, 13, 0.0), reps=30, warm=5)
+    us_gamma = 1e3 * gpu_ms(lambda: intensity_2d_(o_img, gammas, [0] * B, 13, 0.0), reps=30, warm=5)
+    px = B * S * S
+    emit(row="TrainTransform2D full list", config=f"{B}x{C}x{S}^2 fp32 + uint8 labels, n_cls {n_cls}, transform_2d [1,3,4,6,7,8,9,10]",
+         gpu_us=us, default_chain_us=us_default, label_bbox_2d_us=us_bbox, zoom_2d_alone_us=us_zoom,
+         intensity_2d_gamma_and_noise_on_every_sample_us=us_int, intensity_2d_gamma_alone_us=us_gamma,
+         algorithmic_bytes_zoom=(8 * C + 2) * px, achieved_GBps_zoom=(8 * C + 2) * px / us_zoom / 1e3,
+         algorithmic_bytes_intensity=8 * C * px, achieved_GBps_intensity=8 * C * px / us_int / 1e3, hbm_peak_GBps=8000)
+
+
 if sys.argv[1:] == ["augment"]:
     augment_row()
     sys.exit(0)
 if sys.argv[1:] == ["augment2d"]:
     augment2d_row()
+    sys.exit(0)
+if sys.argv[1:] == ["transforms2d"]:
+    transforms2d_row()
     sys.exit(0)
 
 g = torch.Generator().manual_seed(7)
@@ -209,6 +249,7 @@ emit(row="8f-3 mr_normalize_", config=f"{C}x{S}^3 fp32 in place (clone time {ms0
 
 augment_row()
 augment2d_row()
+transforms2d_row()
 
 # ---- 8f-2: sliding-window inference
 from models.HDenseFormer import HDenseFormer
