@@ -249,6 +249,18 @@ int hdf_intensity_2d(float* image, int batch, int channels, int H, int W, const 
   return hdf_launch_intensity2d(image, batch, (int64_t)channels * H * W, gamma, noise, seed, low_clip,
                                 (hipStream_t)stream);
 }
+int64_t hdf_resize_workspace_bytes(int Di, int Hi, int Wi, int Do, int Ho, int Wo) {
+  return hdf_resize_ws_bytes(Di, Hi, Wi, Do, Ho, Wo);
+}
+int hdf_resize_3d(const float* image, const uint8_t* labels, int channels, int n_cls, int Di, int Hi, int Wi, int Do, int Ho,
+                  int Wo, float* image_out, uint8_t* labels_out, void* workspace, int64_t workspace_bytes,
+                  hdf_stream stream) {
+  return hdf_launch_resize3d(image, labels, channels, n_cls, Di, Hi, Wi, Do, Ho, Wo, image_out, labels_out, workspace,
+                             workspace_bytes, (hipStream_t)stream);
+}
+int hdf_trunc_normalize(float* image, int64_t n, float lo, float hi, hdf_stream stream) {
+  return hdf_launch_trunc_normalize(image, n, lo, hi, (hipStream_t)stream);
+}
 int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   float grad_scale, hdf_stream stream) {

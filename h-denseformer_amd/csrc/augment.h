@@ -66,3 +66,23 @@ size_t hdf_norm_ws_bytes(int C);
 int hdf_launch_normalize(float* img, int C, int64_t V, int mode, float pmean, float pw, void* ws, hipStream_t st);
 // class maps [N][V] uint8 -> one-hot [N][C][V] fp32 (labels outside [1, C) count as background)
 int hdf_launch_onehot(const uint8_t* lab, float* oh, int N, int C, int64_t V, hipStream_t st);
+
+// one axis of skimage.transform.resize(order=1) as scipy computes it (resize.hip): n_in -> n_out samples, f = n_in / n_out,
+// the 2r + 1 normalised Gaussian weights of the anti-aliasing filter (r = 0, w = {1}: none), constant != 0 for scipy's
+// 'grid-constant' with cval 0 (labels), else 'mirror' (image).  Computed on the host in fp64 and passed to the kernel by
+// value: r <= 14 at the factor cap of 8.
+constexpr int RESIZE_MAX_RADIUS = 14;
+struct ResizeAxis {
+  int n_in, n_out, r, constant;
+  double f;
+  double w[2 * RESIZE_MAX_RADIUS + 1];
+};
+
+// CropResize's resize of one sample (data_utils/data_loader.py:103-119): image [C][Di][Hi][Wi] fp32 -> image_out
+// [C][Do][Ho][Wo], labels [Di][Hi][Wi] uint8 -> labels_out [Do][Ho][Wo]; either pair may be null.  At most three launches
+// per image channel and per class 1 .. n_cls-1; ws holds the fp64 intermediates of ONE plane.  -1: shapes out of range
+int64_t hdf_resize_ws_bytes(int Di, int Hi, int Wi, int Do, int Ho, int Wo);
+int hdf_launch_resize3d(const float* image, const uint8_t* labels, int C, int n_cls, int Di, int Hi, int Wi, int Do, int Ho,
+                        int Wo, float* image_out, uint8_t* labels_out, void* ws, int64_t ws_bytes, hipStream_t st);
+// Trunc_and_Normalize in place (data_utils/data_loader.py:16-36): ((x - lo) clamped to [0, hi - lo]) / (hi - lo) in fp32
+int hdf_launch_trunc_normalize(float* image, int64_t n, float lo, float hi, hipStream_t st);

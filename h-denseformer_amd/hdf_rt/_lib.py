@@ -75,6 +75,9 @@ _PROTOS = {
     "hdf_label_bbox_2d": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "hdf_zoom_2d": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "hdf_intensity_2d": (_i, [_vp, _i, _i, _i, _i, _pd, _vp, _u64, _f, _vp]),
+    "hdf_resize_workspace_bytes": (_i64, [_i] * 6),
+    "hdf_resize_3d": (_i, [_vp, _vp, _i, _i] + [_i] * 6 + [_vp, _vp, _vp, _i64, _vp]),
+    "hdf_trunc_normalize": (_i, [_vp, _i64, _f, _f, _vp]),
     "hdf_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _vp]),
     "hdf_optim_step": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp, _vp]),
     "hdf_op_to_channels_last": (_i, [_i, _vp, _vp, _i, _i, _i, _i64, _vp]),

@@ -4,6 +4,11 @@ hdf_rt.inference, and RandomTranslationRotationZoom3D + RandomFlip3D + To_Tensor
 (hdf_augment_3d, csrc/augment.hip).  The random draws stay on the host and follow the reference's order, so seeding
 np.random / random reproduces its parameters.  No CPU fallback.
 
+The other 3-D chain, transform_3d = [2,3,4,5,6] (config.py:116): the whole volume is normalised, CropResize (3) brings it to
+input_shape -- resize_3d / crop_resize, skimage's anti-aliased resize as at most three separable gather passes per plane
+(hdf_resize_3d, csrc/resize.hip) -- and the warp, flip and one-hot follow.  Trunc_and_Normalize (7) is trunc_normalize_.
+TrainTransform3D.from_ids maps the reference's ids 1..8.
+
 The default 2-D chain (trainer.py:152-172 with config.py's transform_2d = [1,6,7,10]): MRNormalize per plane, then
 RandomRotate2D + RandomFlip2D + To_Tensor ONE gather kernel per batch (hdf_augment_2d), bit for bit what PIL computes
 on the host (pinned to PIL 12.2.0; include/hdf.h).  The matrix is built here, in Python, because PIL rounds the cosine
@@ -101,25 +106,202 @@ def augment_3d(image, labels, n_cls, affine, flip_h=False, flip_w=False, out_ima
     return out_image, out_onehot
 
 
+_RESIZE_WS = {}      # (device, source shape, result shape) -> the fp64 intermediates of one plane
+_RESIZE_WS_KEEP = 8  # shapes kept, the most recently used last: a dataset of many volume sizes does not pile them up
+
+
+def _shape3(shape, what):
+    try:
+        out = tuple(int(v) for v in shape)
+    except TypeError:
+        out = ()
+    if len(out) != 3 or any(int(v) != v for v in shape):
+        raise ValueError(f"{what} must be three integers (D, H, W), got {shape!r}")
+    return out
+
+
+def resize_3d(image, labels, n_cls, out_shape, out_image=None, out_labels=None):
+    """The resize of CropResize (data_utils/data_loader.py:103-119) of one sample: image fp32 device tensor [C, D, H, W]
+    -> [C, *out_shape], each channel skimage.transform.resize(., out_shape, anti_aliasing=True); labels uint8 device
+    tensor [D, H, W] -> uint8 [*out_shape], the per-class resize(mode='constant') >= 0.5 with the last class winning.
+    Either may be None.  Returns (image, labels): new tensors, or out_image / out_labels when given.  The fp64
+    intermediates of one plane live in a workspace cached per (device, shapes), the last few shapes kept.  Semantics:
+    include/hdf.h, hdf_resize_3d."""
+    first = image if image is not None else labels
+    if first is None:
+        raise ValueError("resize_3d needs an image, labels or both")
+    if not torch.is_tensor(first) or first.device.type != "cuda":
+        raise _lib.HdfError("resize_3d needs device tensors (there is no CPU path)")
+    dev = first.device
+    dst = _shape3(out_shape, "out_shape")
+    c = 0
+    if image is not None:
+        if image.dtype != torch.float32 or image.dim() != 4:
+            raise ValueError(f"image must be a float32 tensor [C, D, H, W], got {image.dtype} {tuple(image.shape)}")
+        image = image.contiguous()
+        c, src = int(image.shape[0]), tuple(int(v) for v in image.shape[1:])
+    if labels is not None:
+        if (not torch.is_tensor(labels) or labels.device != dev or labels.dtype != torch.uint8 or labels.dim() != 3
+                or (image is not None and tuple(labels.shape) != src)):
+            raise ValueError(f"labels must be a uint8 tensor {src if image is not None else '[D, H, W]'} on {dev}")
+        labels = labels.contiguous()
+        src = tuple(int(v) for v in labels.shape)
+
+    def out(t, shape, dtype, what):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        if (not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or tuple(t.shape) != shape
+                or not t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor {shape} on {dev}")
+        return t
+
+    if image is None and out_image is not None:
+        raise ValueError("out_image needs an image")
+    if labels is None and out_labels is not None:
+        raise ValueError("out_labels needs labels")
+    if image is not None:
+        out_image = out(out_image, (c,) + dst, torch.float32, "out_image")
+    if labels is not None:
+        out_labels = out(out_labels, dst, torch.uint8, "out_labels")
+    nbytes = int(lib().hdf_resize_workspace_bytes(*src, *dst))
+    if nbytes < 0:
+        raise ValueError(f"resize_3d: {src} -> {dst} is outside the kernel's limits: every dimension 1..1024, no axis "
+                         f"shrinking by more than a factor of 8")
+    key = (dev, src, dst)
+    ws = _RESIZE_WS.pop(key, None)
+    if ws is None:
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+    _RESIZE_WS[key] = ws
+    while len(_RESIZE_WS) > _RESIZE_WS_KEEP:
+        del _RESIZE_WS[next(iter(_RESIZE_WS))]
+    check(lib().hdf_resize_3d(ptr(image), ptr(labels), c, n_cls, *src, *dst, ptr(out_image), ptr(out_labels), ptr(ws),
+                              nbytes, stream_ptr()), "hdf_resize_3d")
+    return out_image, out_labels
+
+
+def crop_resize(image, labels, n_cls, dim, crop=0):
+    """CropResize.__call__ (data_utils/data_loader.py:85-123) on device tensors: with crop != 0 image and labels become
+    [..., crop:-crop, crop:-crop] -- the last two axes only --, then resize_3d to `dim` when labels.shape != dim.  A 2-D
+    sample (image [C, H, W], labels [H, W], dim of two) goes through as [C, 1, H, W] / [1, H, W].  Returns (image,
+    labels); without a resize they are the (sliced) arguments themselves, as in the reference."""
+    if not torch.is_tensor(image) or image.device.type != "cuda":
+        raise _lib.HdfError("crop_resize needs device tensors (there is no CPU path)")
+    crop = int(crop)
+    if crop != 0:
+        image = image[..., crop:-crop, crop:-crop]
+        labels = labels[..., crop:-crop, crop:-crop]
+    if dim is None or tuple(labels.shape) == tuple(int(v) for v in dim):
+        return image, labels
+    if labels.dim() == 2:
+        if len(dim) != 2 or image.dim() != 3:
+            raise ValueError(f"a 2-D sample is image [C, H, W], labels [H, W] and dim (H, W), got {tuple(image.shape)}, "
+                             f"{tuple(labels.shape)} and {dim!r}")
+        out_i, out_l = resize_3d(image[:, None], labels[None], n_cls, (1,) + tuple(dim))
+        return out_i[:, 0], out_l[0]
+    return resize_3d(image, labels, n_cls, dim)
+
+
+def trunc_normalize_(image, scale):
+    """Trunc_and_Normalize(scale) (data_utils/data_loader.py:16-36) in place on an fp32 device tensor of any shape:
+    ((x - scale[0]) clamped to [0, scale[1] - scale[0]]) / (scale[1] - scale[0]), bit for bit numpy's fp32 sequence.
+    Returns image."""
+    if not torch.is_tensor(image) or image.device.type != "cuda":
+        raise _lib.HdfError("trunc_normalize_ needs a device tensor (there is no CPU path)")
+    if image.dtype != torch.float32 or not image.is_contiguous():
+        raise ValueError(f"image must be a contiguous float32 tensor, got {image.dtype} with strides {image.stride()}")
+    if scale is None or len(scale) != 2:
+        raise ValueError(f"scale must be a pair (lo, hi), got {scale!r}")
+    check(lib().hdf_trunc_normalize(ptr(image), image.numel(), float(scale[0]), float(scale[1]), stream_ptr()),
+          "hdf_trunc_normalize")
+    return image
+
+
+# the reference's transform_list_3d (trainer.py:128-142) by id
+TRANSFORM_3D_NAMES = {1: "RandomCrop3D", 2: "PETandCTNormalize", 3: "CropResize", 4: "RandomTranslationRotationZoom3D",
+                      5: "RandomFlip3D", 6: "To_Tensor", 7: "Trunc_and_Normalize", 8: "MRNormalize"}
+# the orders from_ids accepts: the subsequences of this list of slots
+_SLOTS_3D = ((1,), (2, 7, 8), (3,), (4,), (5,), (6,), (7,))
+_ORDER_3D = "1, one of 2 | 7 | 8, 3, 4, 5, 6, 7"
+
+
 class TrainTransform3D:
     """transform_3d = [1,2,4,5,6] (normalize='petct') or [1,8,4,5,6] ('mr') of trainer.py:128-146 on device tensors:
     RandomCrop3D -> normalisation -> RandomTranslationRotationZoom3D(mode) -> RandomFlip3D(flip) -> To_Tensor.
     mode='' and flip='' give the validation chain (trainer.py:147-150: crop, normalise, one-hot).  The crop comes before
-    the warp, so the warp's zero border is the border of the crop."""
+    the warp, so the warp's zero border is the border of the crop.
 
-    def __init__(self, n_cls, patch_size=None, normalize=None, mode="tr", flip="hv"):
-        if normalize not in (None, "petct", "mr"):
-            raise ValueError(f"normalize must be None, 'petct' or 'mr', got {normalize!r}")
+    Off unless asked for, by keyword: resize=dim with crop runs CropResize(dim, crop=crop) between the normalisation and
+    the warp ([2,3,4,5,6] of config.py:116: the WHOLE volume is normalised and resized to dim, which draws nothing);
+    normalize='trunc' with scale=(lo, hi) is Trunc_and_Normalize as the normaliser ([1,7,4,5,6]); trunc_after=True
+    applies it to the image after the one-hot ([...,6,7]).  from_ids maps the reference's ids."""
+
+    def __init__(self, n_cls, patch_size=None, normalize=None, mode="tr", flip="hv", *, resize=None, crop=0, scale=None,
+                 trunc_after=False):
+        if normalize not in (None, "petct", "mr", "trunc"):
+            raise ValueError(f"normalize must be None, 'petct', 'mr' or 'trunc', got {normalize!r}")
+        if (normalize == "trunc" or trunc_after) and (scale is None or len(scale) != 2 or not scale[1] > scale[0]):
+            raise ValueError(f"Trunc_and_Normalize needs scale=(lo, hi) with hi > lo, got {scale!r}")
+        if resize is not None:
+            resize = _shape3(resize, "resize")
+        if int(crop) < 0 or (crop and resize is None):
+            raise ValueError(f"crop={crop!r}: a non-negative margin of CropResize, which needs resize=dim")
         self.n_cls, self.patch_size, self.normalize, self.mode, self.flip = n_cls, patch_size, normalize, mode, flip
+        self.resize, self.crop, self.trunc_after = resize, int(crop), bool(trunc_after)
+        self.scale = None if scale is None else (scale[0], scale[1])
+
+    @classmethod
+    def from_ids(cls, n_cls, transform_3d, input_shape=None, patch_size=None, crop=0, scale=None, train=True):
+        """The chain the reference builds from config.py's transform_3d (trainer.py:128-150): ids into its list, run in
+        the order given.  1 RandomCrop3D(patch_size), 2 PETandCTNormalize, 3 CropResize(input_shape, crop), 4
+        RandomTranslationRotationZoom3D('tr'), 5 RandomFlip3D('hv'), 6 To_Tensor, 7 Trunc_and_Normalize(scale), 8
+        MRNormalize.  Accepted orders: the subsequences of 1, one of 2 | 7 | 8, 3, 4, 5, 6, 7 (a 7 before the one-hot is
+        the normaliser, one after it rescales the finished image); anything else raises ValueError.  6 must be present:
+        the chain returns the one-hot.  train=False keeps ids 1, 2, 3 and 6 only, as trainer.py:147-150 does -- which
+        drops the normalisers 7 and 8 from the validation chain; the quirk is kept."""
+        ids = [int(i) for i in transform_3d]
+        for i in ids:
+            if i not in TRANSFORM_3D_NAMES:
+                raise ValueError(f"transform_3d id {i} is not in the reference's list (1..8)")
+        if not train:
+            ids = [i for i in ids if i in (1, 2, 3, 6)]
+        slot, taken = 0, {}
+        for i in ids:
+            while slot < len(_SLOTS_3D) and i not in _SLOTS_3D[slot]:
+                slot += 1
+            if slot == len(_SLOTS_3D):
+                raise ValueError(f"transform_3d {ids} does not run on the device: the accepted order is a subsequence of "
+                                 f"{_ORDER_3D}")
+            taken[slot] = i
+            slot += 1
+        if 5 not in taken:
+            raise ValueError("transform_3d must hold 6 (To_Tensor): the chain returns the one-hot")
+        if 0 in taken and patch_size is None:
+            raise ValueError("transform_3d id 1 (RandomCrop3D) needs patch_size")
+        if 2 in taken and input_shape is None:
+            raise ValueError("transform_3d id 3 (CropResize) needs input_shape")
+        return cls(n_cls, patch_size=patch_size if 0 in taken else None,
+                   normalize={None: None, 2: "petct", 7: "trunc", 8: "mr"}[taken.get(1)],
+                   mode="tr" if 3 in taken else "", flip="hv" if 4 in taken else "",
+                   resize=input_shape if 2 in taken else None, crop=crop if 2 in taken else 0,
+                   scale=scale if (taken.get(1) == 7 or 6 in taken) else None, trunc_after=6 in taken)
+
+    def draw(self, shape):
+        """The random parameters of one sample whose labels have `shape`, drawn in the reference's order and nothing
+        else: the crop origin (random; None without a patch), the warp's matrix (np.random) and the flip flags
+        (np.random).  The resize and the normalisers draw nothing."""
+        origin = None
+        if self.patch_size is not None:
+            origin = crop_origin(shape, tuple(int(v) for v in self.patch_size))
+        return origin, trz_matrix(self.mode), flip_flags(self.flip)
 
     def __call__(self, image, labels):
         """image: raw fp32 [C, Ds, Hs, Ws], labels: uint8 [Ds, Hs, Ws], both on the device.  Returns (image [C, D, H, W],
         onehot [n_cls, D, H, W]); the arguments are left untouched."""
         if not torch.is_tensor(image) or image.device.type != "cuda":
             raise _lib.HdfError("TrainTransform3D needs device tensors (there is no CPU path)")
-        if self.patch_size is not None:
+        o, affine, flips = self.draw(labels.shape)
+        if o is not None:
             p = tuple(int(v) for v in self.patch_size)
-            o = crop_origin(labels.shape, p)
             image = image[:, o[0]:o[0] + p[0], o[1]:o[1] + p[1], o[2]:o[2] + p[2]]
             labels = labels[o[0]:o[0] + p[0], o[1]:o[1] + p[1], o[2]:o[2] + p[2]]
         image = image.clone(memory_format=torch.contiguous_format)     # the normalisation works in place
@@ -128,9 +310,18 @@ class TrainTransform3D:
             pet_ct_normalize_(image)
         elif self.normalize == "mr":
             mr_normalize_(image)
+        elif self.normalize == "trunc":
+            trunc_normalize_(image, self.scale)
+        if self.resize is not None:
+            image, labels = crop_resize(image, labels, self.n_cls, self.resize, self.crop)
+            image, labels = image.contiguous(), labels.contiguous()
         if not self.mode and not self.flip:
-            return image, onehot_from_labels(labels[None], self.n_cls)[0]
-        return augment_3d(image, labels, self.n_cls, trz_matrix(self.mode), *flip_flags(self.flip))
+            image, onehot = image, onehot_from_labels(labels[None], self.n_cls)[0]
+        else:
+            image, onehot = augment_3d(image, labels, self.n_cls, affine, *flips)
+        if self.trunc_after:
+            trunc_normalize_(image, self.scale)
+        return image, onehot
 
 
 # ---------------------------------------------------------------------------------------------------------- 2-D chain

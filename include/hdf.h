@@ -399,6 +399,46 @@ int hdf_zoom_2d(const float* image, const uint8_t* labels, int batch, int channe
 int hdf_intensity_2d(float* image, int batch, int channels, int H, int W, const double* gamma, const uint8_t* noise,
                      uint64_t seed, float low_clip, hdf_stream stream);
 
+/* ---- CropResize of the 3-D transform list (id 3 of trainer.py:128-142; data_utils/data_loader.py:71-123): the resize of
+ * one sample to the network's input shape.  image [channels][Di][Hi][Wi] fp32 -> image_out [channels][Do][Ho][Wo], each
+ * channel what skimage.transform.resize(image[i], dim, anti_aliasing=True) computes; labels [Di][Hi][Wi] uint8 ->
+ * labels_out [Do][Ho][Wo]: for z = 1 .. n_cls-1 ascending, roi = resize((label == z) as fp32, dim, mode='constant') and
+ * out[roi >= 0.5] = z -- the LAST class that reaches 0.5 wins, a class beats background at exactly 0.5, label values
+ * >= n_cls match no class and become background.  The indicator is formed while the class map is read; no mask is stored.
+ * resize(order=1) of scikit-image >= 0.19 is scipy, and this entry restates scipy 1.15 (agreement with scikit-image
+ * itself is by reading its source, not by measurement).  Per axis, n_in -> n_out samples:
+ *   f = n_in / n_out; sigma = max(0, (f - 1) / 2); an axis with sigma <= 1e-15 is not filtered; else
+ *   gaussian_filter(truncate=4): radius r = int(4 sigma + 0.5), weights exp(-0.5 k^2 / sigma^2), k = -r..r, normalised to
+ *   sum 1; then zoom(order=1, grid_mode=True): output index o reads the source coordinate c = (o + 0.5) f - 0.5, linear
+ *   between floor(c) and floor(c) + 1.
+ *   boundary, in the filter and in the interpolation alike: image 'mirror' -- index p reads p' = |p| mod (2 n_in - 2), or
+ *   2 n_in - 2 - p' when p' >= n_in (0 when n_in = 1), as often as the radius needs; labels 'grid-constant' with cval 0 -- a
+ *   sample outside [0, n_in) is 0.
+ * The three axes commute.  scipy rounds to fp32 after every filtered axis and after the interpolation; this entry does
+ * NOT: one axis is one banded operator (the interpolation row applied to the filter rows, at most 2r + 2 = 30 taps), the
+ * operators are applied one after the other with fp64 accumulation and fp64 intermediates, and the result is rounded to
+ * fp32 once, or compared with 0.5 in fp64.  It therefore differs from live scipy by scipy's own roundings: at most
+ * (g + 1) 2^-24 max|image| with g filtered axes.  Class maps equal scipy's except where a class sum lies within 1e-7 of
+ * 0.5 (an exact factor 2 puts edges there), where scipy's outcome is its rounding noise; there the result is unspecified.
+ * skimage's final clip to the input range is a no-op (all weights are non-negative).
+ * Either pair image / image_out or labels / labels_out may be null (a labels-only or an image-only call), not both.
+ * Equal shapes are legal and give a copy (labels: values >= n_cls become 0).
+ * workspace: hdf_resize_workspace_bytes(...) bytes, 8-byte aligned: the fp64 intermediates of ONE plane (the planes take
+ * turns), 0 when at most one axis changes its size; -1 for shapes that hdf_resize_3d refuses.
+ * Refused with HDF_ERR_ARG and a "resize_3d:" message before any launch: a dimension outside 1..1024; n_in > 8 n_out on
+ * an axis (the cap that bounds the taps); n_cls outside 2..8; channels outside 0..64 (0 only without an image); a half
+ * pair; no pair; a workspace that is too small; an output or the workspace overlapping any other buffer.
+ * At most 3 (channels + n_cls - 1) launches, no host synchronisation, no copy, no allocation. */
+int64_t hdf_resize_workspace_bytes(int Di, int Hi, int Wi, int Do, int Ho, int Wo);
+int hdf_resize_3d(const float* image, const uint8_t* labels, int channels, int n_cls, int Di, int Hi, int Wi, int Do, int Ho,
+                  int Wo, float* image_out, uint8_t* labels_out, void* workspace, int64_t workspace_bytes,
+                  hdf_stream stream);
+
+/* Trunc_and_Normalize (ids 7 / 11; data_utils/data_loader.py:16-36) in place on n fp32 values, bit for bit the numpy
+ * sequence: x = x - lo; x < 0 -> 0; x > hi - lo -> hi - lo; x = x / (hi - lo), every step in fp32 (hi - lo is formed
+ * in fp32 too).  Refused with a "trunc_normalize:" message: a null image, n < 1, hi <= lo, a value that is not finite. */
+int hdf_trunc_normalize(float* image, int64_t n, float lo, float hi, hdf_stream stream);
+
 /* ---- optimizer: torch.optim.Adam as configured by trainer.py:793-840 (L2 weight decay on the mask) ---- */
 int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,

@@ -5,6 +5,7 @@ bounded host-side restatement of what the reference does for the same call (nump
   python tools/bench_rows.py augment                            (the 3-D augmentation row alone)
   python tools/bench_rows.py augment2d                          (the 2-D training chain row alone)
   python tools/bench_rows.py transforms2d                       (the full 2-D transform list row alone)
+  python tools/bench_rows.py resize3d                           (the CropResize row alone)
 """
 import json
 import os
@@ -179,6 +180,54 @@ def transforms2d_row(B=24, C=3, n_cls=2, S=384):
          algorithmic_bytes_intensity=8 * C * px, achieved_GBps_intensity=8 * C * px / us_int / 1e3, hbm_peak_GBps=8000)
 
 
+def resize3d_row(C=2, n_cls=3, src=(173, 191, 205), S=144):
+    """one crop_resize call (hdf_resize_3d: three gather passes per image channel and per foreground class) on a
+    2 x 173x191x205 sample to 144^3, next to the host sequence it replaces, timed on this box on one thread: per plane
+    scipy.ndimage.gaussian_filter + zoom(order=1, grid_mode=True) in fp32 arrays, the arithmetic of
+    skimage.transform.resize (data_loader.py:103-119); plus the whole [2,3,4,5,6] chain on the same sample"""
+    from hdf_rt import TrainTransform3D, crop_resize
+    gen = torch.Generator().manual_seed(14)
+    img = torch.randn((C,) + src, generator=gen).to(DEV)
+    lab_h = torch.randint(0, n_cls, tuple(-(-s // 8) for s in src), generator=gen, dtype=torch.uint8)
+    lab_h = lab_h.repeat_interleave(8, 0).repeat_interleave(8, 1).repeat_interleave(8, 2)[:src[0], :src[1], :src[2]]
+    lab = lab_h.contiguous().to(DEV)
+    dim = (S, S, S)
+    us = 1e3 * gpu_ms(lambda: crop_resize(img, lab, n_cls, dim), reps=30, warm=5)
+    np.random.seed(14)
+    tf = TrainTransform3D.from_ids(n_cls, [2, 3, 4, 5, 6], input_shape=dim)
+    us_chain = 1e3 * gpu_ms(lambda: tf(img, lab), reps=30, warm=5)
+    vi, vo = src[0] * src[1] * src[2], S ** 3
+    by = (4 * C + (n_cls - 1)) * vi + (4 * C + (n_cls - 1)) * vo     # sources read once per plane, results written
+    try:
+        from scipy import ndimage as ndi
+        img_np, lab_np = img.cpu().numpy(), lab_h.numpy()
+        sigma = [max(0.0, (i / o - 1) / 2) for i, o in zip(src, dim)]
+        zoom = [o / i for i, o in zip(src, dim)]
+
+        def ref_chain():
+            for ch in img_np:
+                ndi.zoom(ndi.gaussian_filter(ch, sigma, mode="mirror", cval=0), zoom, order=1, mode="mirror", cval=0,
+                         grid_mode=True)
+            out = np.zeros(dim, dtype=np.float32)
+            for z in range(1, n_cls):
+                roi = ndi.zoom(ndi.gaussian_filter((lab_np == z).astype(np.float32), sigma, mode="grid-constant", cval=0),
+                               zoom, order=1, mode="grid-constant", cval=0, grid_mode=True)
+                out[roi >= 0.5] = z
+
+        import scipy
+        cpu = {"kind": "port", "what": f"scipy {scipy.__version__} gaussian_filter + zoom(order 1, grid_mode), {C + n_cls - 1} "
+                                       f"planes of {src} -> {S}^3 (data_loader.py:103-119)",
+               "s_per_sample": cpu_s(ref_chain, reps=3), "threads": 1}
+    except ImportError as exc:
+        cpu = {"kind": "not measured", "what": repr(exc)}
+    emit(row="crop_resize", config=f"{C}x{src[0]}x{src[1]}x{src[2]} fp32 + uint8 labels -> {S}^3, n_cls {n_cls}",
+         gpu_us=us, launches=3 * (C + n_cls - 1), chain_2_3_4_5_6_us=us_chain, algorithmic_bytes=by,
+         achieved_GBps=by / us / 1e3, hbm_peak_GBps=8000, cpu_baseline=cpu)
+
+
+if sys.argv[1:] == ["resize3d"]:
+    resize3d_row()
+    sys.exit(0)
 if sys.argv[1:] == ["augment"]:
     augment_row()
     sys.exit(0)
