@@ -56,6 +56,10 @@ _PROTOS = {
                                     _vp, _vp, _vp]),
     "hdf_loss_focal_backward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _i,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hdf_loss_topk_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "hdf_loss_topk_forward": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "hdf_loss_topk_backward": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hdf_op_topk_select": (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "hdf_dice_counts": (_i, [_i, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "hdf_confusion_matrix": (_i, [_i, _vp, _vp, _i, _i, _i64, _vp, _i, _vp]),
     "hdf_confusion_matrix_labels": (_i, [_vp, _vp, _i, _i64, _vp, _i, _vp]),

@@ -1,6 +1,6 @@
 """Fused DeepSuperloss(CEPlusDice) and DeepSuperloss(FocalLoss / FLPlusDice) on the GPU: one autograd node each, one
-pass over the logits per scale (hdf_loss_weighted_* / hdf_loss_focal_* in include/hdf.h).  Reference:
-loss/combine_loss.py:8-79, loss/cross_entropy.py:45-73."""
+pass over the logits per scale (hdf_loss_weighted_* / hdf_loss_focal_* in include/hdf.h); TopKLoss: one node per scale
+(hdf_loss_topk_*).  Reference: loss/combine_loss.py:8-79, loss/cross_entropy.py:26-73."""
 import torch
 
 from . import _lib
@@ -160,6 +160,114 @@ class DeepSuperFocalDice(torch.autograd.Function):
                                             *ctx.args, ptr(ws), ptr(gg), pd[0], pd[1], pd[2], pd[3], stream_ptr()),
               "hdf_loss_focal_backward")
         return (None, *douts)
+
+
+TOPK_REDUCTIONS = (None, "mean", "sum", "topk")
+
+
+def topk_count(num_voxels, k):
+    """K of TopKLoss, the reference's expression verbatim (loss/cross_entropy.py:36)"""
+    return int(num_voxels * k / 100)
+
+
+def topk_settings(weight, ignore_index, k, reduction):
+    """TopKLoss(weight, ignore_index, k, reduction) settings, checked where the module is built.  A negative class weight is
+    refused: the selection orders the per-voxel losses by bit pattern, which needs them non-negative."""
+    if reduction not in TOPK_REDUCTIONS:
+        raise ValueError(f"TopKLoss: reduction must be one of {TOPK_REDUCTIONS} (got {reduction!r})")
+    if not (ignore_index == -100 or (isinstance(ignore_index, int) and ignore_index >= 0)):
+        raise ValueError(f"TopKLoss: ignore_index must be -100 or a class index (got {ignore_index!r})")
+    if not k >= 0:
+        raise ValueError(f"TopKLoss: k must be a non-negative percentage (got {k!r})")
+    if weight is not None:
+        w = torch.as_tensor(weight).detach().float().flatten()
+        if bool((w < 0).any()) or bool(torch.isnan(w).any()):
+            raise ValueError("TopKLoss: class weights must be non-negative (the top-k selection orders the weighted "
+                             "per-voxel losses by bit pattern)")
+
+
+TOPK_SELECT_WORKSPACE_BYTES = 65536        # HDF_TOPK_SELECT_WORKSPACE_BYTES of include/hdf.h
+
+
+def topk_workspace_views(ws, n):
+    """(res fp32 [n], rank int32 [n]) inside a workspace of hdf_loss_topk_forward over n voxels: the per-voxel losses and
+    each voxel's position in the output (-1: not selected), as include/hdf.h lays them out"""
+    pitch = (4 * n + 255) // 256 * 256
+    o = TOPK_SELECT_WORKSPACE_BYTES
+    return ws[o:o + 4 * n].view(torch.float32), ws[o + pitch:o + pitch + 4 * n].view(torch.int32)
+
+
+class TopKVoxelCE(torch.autograd.Function):
+    """apply((target, weight, ignore_index, k, mean, scale_shift), logits): the K = int(N * k / 100) largest per-voxel
+    weighted cross-entropy values of logits [B,C,D,H,W] / [B,C,H,W] against the FULL-resolution one-hot target read at
+    index << scale_shift (nearest down-sampling by 2^scale_shift without a copy; 3-D logits of depth 1 with a shift are
+    refused: depth 1 means 2-D to the kernels).  mean False: the fp32 K-vector in voxel
+    order (the reference's TopKLoss for reduction None / 'mean' / 'sum', loss/cross_entropy.py:26-43, which leaves the
+    order open); mean True: their fp32 scalar mean (reduction='topk').  The workspace (per-voxel losses and ranks) is a
+    torch allocation saved for backward; the upstream gradient is read on the device; nothing synchronises."""
+
+    @staticmethod
+    def forward(ctx, spec, logits):
+        target, cw, ignore, k, mean, shift = spec
+        if logits.dtype not in _DT:
+            raise _lib.HdfError(f"TopKLoss: logits must be float32, bfloat16 or float16 (got {logits.dtype})")
+        if target.dim() not in (4, 5) or not 0 <= shift <= 3:
+            raise _lib.HdfError(f"TopKLoss: target must be [B,C,D,H,W] or [B,C,H,W] (got {tuple(target.shape)}), "
+                                f"scale_shift 0..3 (got {shift})")
+        b, c = target.shape[:2]
+        sp = tuple(target.shape[2:])
+        if any(v % (1 << shift) for v in sp) or tuple(logits.shape) != (b, c) + tuple(v >> shift for v in sp):
+            raise AssertionError(f"predict & target shape do not match at scale {shift}: {tuple(logits.shape)} against "
+                                 f"{tuple(target.shape)}")
+        if not (ignore == -100 or 0 <= ignore < c):
+            raise ValueError(f"TopKLoss: ignore_index {ignore} is neither -100 nor a class in [0, {c})")
+        lsp = tuple(logits.shape[2:])
+        if len(lsp) == 3 and lsp[0] == 1 and shift:
+            # the kernels read depth 1 as 2-D logits, whose target keeps depth 1 at every scale
+            raise _lib.HdfError(f"TopKLoss: 3-D logits of depth 1 at scale_shift {shift} (a target of depth {1 << shift}) "
+                                f"are not supported; pass 2-D logits and a 2-D target")
+        d, h, w = ((1,) + lsp) if len(lsp) == 2 else lsp
+        n = b * d * h * w
+        kk = topk_count(n, k)
+        ctx.kk = kk
+        if kk == 0:
+            if mean:
+                raise ValueError(f"TopKLoss(reduction='topk'): K = int({n} * {k} / 100) = 0 voxels (the mean of none)")
+            ctx.like = (logits.shape, logits.dtype, logits.device)
+            return torch.empty(0, dtype=torch.float32, device=logits.device)      # (no launch)
+        if not logits.is_cuda or not target.is_cuda:
+            raise _lib.HdfError("fused loss needs GPU tensors (no CPU fallback)")
+        if cw is not None:
+            cw = _device_class_weight(cw, logits.device)
+            if cw.dim() != 1 or cw.shape[0] != c:
+                raise AssertionError(f"Expect weight shape [{c}], get[{tuple(cw.shape)}]")
+        lg = logits.contiguous()
+        tgt = target.float().contiguous()
+        nbytes = lib().hdf_loss_topk_workspace_bytes(b, d, h, w)
+        if nbytes < 0:
+            raise _lib.HdfError(f"TopKLoss: {n} voxels (fewer than 2^31 supported)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=lg.device)
+        out = torch.empty(() if mean else (kk,), dtype=torch.float32, device=lg.device)
+        geom = (b, c, d, h, w, shift, ptr(cw), ignore, kk)
+        check(lib().hdf_loss_topk_forward(_DT[lg.dtype], ptr(lg), ptr(tgt), *geom, ptr(ws), nbytes,
+                                          None if mean else ptr(out), ptr(out) if mean else None, stream_ptr()),
+              "hdf_loss_topk_forward")
+        ctx.save_for_backward(lg, tgt, ws)
+        ctx.geom, ctx.cw, ctx.mean = geom, cw, mean
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.kk == 0:
+            shape, dtype, device = ctx.like
+            return None, torch.zeros(shape, dtype=dtype, device=device)
+        lg, tgt, ws = ctx.saved_tensors
+        dl = torch.empty_like(lg)
+        gg = g.detach().float().reshape(-1).contiguous()
+        check(lib().hdf_loss_topk_backward(_DT[lg.dtype], ptr(lg), ptr(tgt), *ctx.geom, ptr(ws), ws.numel(),
+                                           None if ctx.mean else ptr(gg), ptr(gg) if ctx.mean else None, ptr(dl),
+                                           stream_ptr()), "hdf_loss_topk_backward")
+        return None, dl
 
 
 def dice_counts(logits, target_onehot):

@@ -3,13 +3,16 @@
 Supported: what trainer.py:743-771 (_get_loss) builds for the H-DenseFormer runs --
 DeepSuperloss(criterion=CEPlusDice(weight=class_weight or None, ignore_index=0)) and, for two-class runs,
 DeepSuperloss(criterion=FocalLoss(reduction='sum')) -- plus FLPlusDice(weight, ignore_index) and ignore_index=None,
-with the BinaryDiceLoss defaults (smooth 1e-5, p 1, reduction 'mean').  Anything else raises: there is no eager
-fallback."""
+with the BinaryDiceLoss defaults (smooth 1e-5, p 1, reduction 'mean'), and DeepSuperloss(criterion=TopKLoss(...,
+reduction='topk')) = sum_i 2^-i * (mean of the K_i largest per-voxel losses of scale i), K_i from that scale's voxel count,
+the target read at index << i (F.interpolate(nearest) by exactly 2^i) without a down-sampled copy.  A TopKLoss in the
+reference's vector form raises here as it does in the reference (four vectors of different lengths cannot be summed).
+Anything else raises: there is no eager fallback."""
 from torch import nn
 
-from hdf_rt.loss_fn import DeepSuperCEDice, DeepSuperFocalDice
+from hdf_rt.loss_fn import DeepSuperCEDice, DeepSuperFocalDice, TopKVoxelCE
 
-from .cross_entropy import FocalLoss
+from .cross_entropy import FocalLoss, TopKLoss
 
 _DICE_DEFAULTS = dict(smooth=1e-5, p=1, reduction="mean")
 
@@ -69,12 +72,23 @@ class DeepSuperloss(nn.Module):
         self.loss = criterion
 
     def forward(self, input, target):
+        if isinstance(self.loss, TopKLoss):
+            if self.loss.reduction != "topk":
+                raise NotImplementedError("DeepSuperloss(TopKLoss): the reference's vector form cannot be summed over "
+                                          "scales (the reference raises too); build TopKLoss(..., reduction='topk')")
+            outs = list(input)                 # (the settings were checked when the criterion was built)
+            if not 1 <= len(outs) <= 4:
+                raise NotImplementedError("fused DeepSuperloss handles 1..4 deep-supervision scales")
+            total = TopKVoxelCE.apply(self.loss._spec(target, 0), outs[0])
+            for i, out in enumerate(outs[1:], 1):
+                total = total + TopKVoxelCE.apply(self.loss._spec(target, i), out) * (1.0 / (1 << i))
+            return total
         if isinstance(self.loss, CEPlusDice):
             node = DeepSuperCEDice
         elif isinstance(self.loss, (FLPlusDice, FocalLoss)):
             node = DeepSuperFocalDice
         else:
-            raise NotImplementedError("fused DeepSuperloss needs criterion=CEPlusDice(...), FLPlusDice(...) or "
-                                      "FocalLoss(...)")
+            raise NotImplementedError("fused DeepSuperloss needs criterion=CEPlusDice(...), FLPlusDice(...), "
+                                      "FocalLoss(...) or TopKLoss(..., reduction='topk')")
         self.loss._check()
         return node.apply(self.loss._spec(target), *list(input))

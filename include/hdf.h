@@ -208,6 +208,49 @@ int hdf_loss_focal_backward(int dtype, const void* out0, const void* out1, const
                             float dice_weight, const float* class_weight, int dice_ignore_index, const void* workspace,
                             const float* grad_out, void* dout0, void* dout1, void* dout2, void* dout3,
                             hdf_stream stream);
+/* ---- TopKLoss (loss/cross_entropy.py:26-43; config.py:125 offers it, trainer.py:751-753 builds it).  Per voxel v of the
+ * logits [batch][n_cls][D][H][W] (D = 1: 2-D logits): res[v] = class_weight[t_v] * nll_v, t_v the arg-max of the one-hot
+ * target (the first maximum wins), nll_v = log(sum_c exp(x_c - max)) - (x_t - max) >= 0 in fp32 from the stored logits;
+ * res[v] = 0 where t_v == ignore_index (-100: none).  The K largest of the n = batch * D * H * W values are selected, K =
+ * int(n * k / 100) formed by the caller as the reference forms it.  The reference's quirks, restated: its constructor hands
+ * reduce=False to torch.nn.CrossEntropyLoss, which overwrites self.reduction with 'none', so for reduction None, 'mean' and
+ * 'sum' alike forward returns the K-vector of torch.topk(res, K, sorted=False) -- in unspecified order, not a scalar: it
+ * cannot be passed to backward() nor through DeepSuperloss, so the reference cannot train with this loss as trainer.py
+ * builds it.  Here the vector's order is defined (ascending voxel index b, d, h, w) and the scalar mean of the K values
+ * (named 'topk' after BinaryDiceLoss's reduction, loss/dice_loss.py:44-46) is the trainable form.
+ *   Tie rule: among values equal to the K-th largest, the lowest voxel index is taken first.
+ *   NaN rule: a NaN value counts as the largest, as in torch.topk; a NaN logit therefore reaches the result.
+ * The target is [batch][n_cls][D << s][H << s][W << s] (depth 1 stays 1) with s = scale_shift in 0..3: nearest
+ * down-sampling by 2^s reads index dst << s (DeepSuperloss, loss/combine_loss.py:68-79), no down-sampled copy is made.
+ * forward: exactly one of values_out [K] (voxel order) and mean_out [1] (the fp64 mean rounded once).  backward: exactly one
+ * of grad_values [K] and grad_mean [1] (device pointers: a GradScaler costs no host synchronisation); dlogits (the logits'
+ * dtype) = g * class_weight[t] * (p_c - [c == t]) on the selected voxels with g = grad_values[rank] or *grad_mean / K (K exact, the quotient rounded to fp32 once),
+ * exact zeros elsewhere and on ignored voxels.  The workspace (res and rank, 8 bytes a voxel, plus
+ * HDF_TOPK_SELECT_WORKSPACE_BYTES) is the caller's, written by forward and read by backward; the library allocates nothing.
+ * Its layout: the select's state (HDF_TOPK_SELECT_WORKSPACE_BYTES), then res fp32 [n], then, 4 n rounded up to a multiple
+ * of 256 bytes later, rank int32 [n] (each voxel's position in the output, -1 = not selected).
+ * Refused before anything is launched (HDF_ERR_ARG, message "topk: ..."): K < 1 or K > n, n >= 2^31, n_cls outside 2..8,
+ * scale_shift outside 0..3, ignore_index outside {-100, 0..n_cls-1}, a workspace below the size function or not aligned
+ * to 16 bytes, batch > 65535 (one grid row a sample), both or neither of the two outputs / gradients.  Logits of depth 1
+ * are 2-D logits to these entries: with scale_shift > 0 their target has depth 1 too, never 1 << s. */
+#define HDF_TOPK_SELECT_WORKSPACE_BYTES 65536
+int64_t hdf_loss_topk_workspace_bytes(int batch, int D, int H, int W); /* D, H, W of the logits; -1 if refused */
+int hdf_loss_topk_forward(int dtype, const void* logits, const float* target_onehot, int batch, int n_cls, int D, int H,
+                          int W, int scale_shift, const float* class_weight, int ignore_index, int64_t K,
+                          void* workspace, int64_t workspace_bytes, float* values_out, float* mean_out,
+                          hdf_stream stream);
+int hdf_loss_topk_backward(int dtype, const void* logits, const float* target_onehot, int batch, int n_cls, int D, int H,
+                           int W, int scale_shift, const float* class_weight, int ignore_index, int64_t K,
+                           const void* workspace, int64_t workspace_bytes, const float* grad_values,
+                           const float* grad_mean, void* dlogits, hdf_stream stream);
+/* the select on its own: the K largest of n floats (device), exact, for any input -- the order is that of the values with
+ * -0.0 below +0.0 and every NaN above +inf; tie and NaN rules as above.  Multi-pass radix select over the 32-bit key; no
+ * sort, no host round trip, integer atomics only (two runs agree in every bit).  workspace: at least
+ * HDF_TOPK_SELECT_WORKSPACE_BYTES, aligned to 16 bytes (refused otherwise, like K < 1, K > n and n >= 2^31).  result[4] (or NULL) = bit pattern of the K-th largest value (a NaN threshold reads
+ * 0x7fc00000), count above it, ties taken, 0; rank_out[n] (or NULL) = position in the output, -1 = not selected;
+ * values_out[K] (or NULL) in index order; mean_out[1] (or NULL). */
+int hdf_op_topk_select(const float* values, int64_t n, int64_t K, void* workspace, int64_t workspace_bytes,
+                       uint64_t* result, int32_t* rank_out, float* values_out, float* mean_out, hdf_stream stream);
 /* hard-argmax Dice counts of trainer.py:919-945: counts[batch][8][3] = (|P&T|, |P|, |T|) per class, uint64.
  * This and hdf_confusion_matrix refuse (HDF_ERR_ARG) batch < 1, voxels < 1 and n_cls outside 1..8. */
 int hdf_dice_counts(int dtype, const void* logits, const float* target_onehot, int batch, int n_cls, int64_t voxels,
