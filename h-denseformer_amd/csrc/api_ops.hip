@@ -180,6 +180,30 @@ int hdf_surface_distances(const uint8_t* target, const uint8_t* prediction, int 
   return hdf_launch_surface_distances(target, prediction, label, D, H, W, workspace, (unsigned long long*)result,
                                       histogram_out, histogram_len, (hipStream_t)stream);
 }
+int64_t hdf_surface_asd_workspace_bytes(int D, int H, int W) {
+  if (hdf_surface_check_dims("asd_workspace_bytes", D, H, W) != HDF_OK) return -1;
+  return hdf_surface_asd_ws_bytes(D, H, W);
+}
+int hdf_op_edge_flags(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W, uint8_t* flags,
+                      uint64_t* counts, hdf_stream stream) {
+  HDF_TRY(hdf_surface_check_dims("edge_flags", D, H, W));
+  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: edge_flags: label %d (1..255)", label);
+  HDF_CHECK_ARG(target && prediction && flags && counts, "surface: edge_flags: null argument");
+  return hdf_launch_edge_flags(target, prediction, label, D, H, W, flags, (unsigned long long*)counts, false,
+                               (hipStream_t)stream);
+}
+int hdf_surface_asd(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W, void* workspace,
+                    int64_t workspace_bytes, uint64_t* result, uint32_t* histogram_out, int64_t histogram_len,
+                    hdf_stream stream) {
+  HDF_TRY(hdf_surface_check_dims("asd", D, H, W));
+  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: asd: label %d (1..255)", label);
+  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_asd_ws_bytes(D, H, W), "surface: asd: workspace of %lld bytes, %lld needed",
+                (long long)workspace_bytes, (long long)hdf_surface_asd_ws_bytes(D, H, W));
+  HDF_CHECK_ARG(histogram_len >= 0, "surface: asd: histogram_len %lld", (long long)histogram_len);
+  HDF_CHECK_ARG(target && prediction && workspace && result, "surface: asd: null argument");
+  return hdf_launch_surface_asd(target, prediction, label, D, H, W, workspace, (unsigned long long*)result, histogram_out,
+                                histogram_len, (hipStream_t)stream);
+}
 int64_t hdf_normalize_workspace_bytes(int channels) { return (int64_t)hdf_norm_ws_bytes(channels); }
 int hdf_normalize_mr(float* image, int channels, int64_t voxels, void* workspace, hdf_stream stream) {
   HDF_CHECK_ARG(image && workspace, "normalize_mr: null argument");

@@ -1,5 +1,6 @@
 // Surface-distance evaluation (surface.hip): mask flags, the exact squared Euclidean distance transform, the gather of
-// surface distances into a histogram and the order-statistic select.  Definitions: include/hdf.h.
+// surface distances into a histogram and the order-statistic select; the average surface distance on top of that
+// transform (surface_asd.hip).  Definitions: include/hdf.h.
 #pragma once
 #include "../../include/hdf.h"  // HDF_EDT_NO_SEED
 #include "hdf_common.h"
@@ -12,6 +13,9 @@ enum {
   HDF_SF_B26_P = 8,
   HDF_SF_C6_T = 16,   // in T with an in-volume face neighbour outside T: the contour
   HDF_SF_C6_P = 32,
+  // set by hdf_op_edge_flags only (surface_asd.hip), which leaves bits 4..32 clear
+  HDF_SF_E6_T = 64,   // in T with a face neighbour outside T, a neighbour outside the volume included: MONAI's edge set
+  HDF_SF_E6_P = 128,
 };
 // "no seed anywhere" is HDF_EDT_NO_SEED (include/hdf.h): + 1023^2 = 1 074 788 352 < 2^31, and every real squared
 // distance (at most 3 * 1023^2) is below it
@@ -29,3 +33,11 @@ int hdf_launch_mask_flags(const uint8_t* tgt, const uint8_t* pred, int label, in
 int hdf_launch_edt_sq(const uint8_t* flags, int seed_mask, int D, int H, int W, int32_t* d2, hipStream_t st);
 int hdf_launch_surface_distances(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, void* ws,
                                  unsigned long long* result, uint32_t* hist_out, int64_t hist_len, hipStream_t st);
+
+// average surface distance (surface_asd.hip).  hdf_surface_asd_ws_bytes >= hdf_surface_ws_bytes for every volume.
+int64_t hdf_surface_asd_ws_bytes(int D, int H, int W);
+// counts_are_zero: the caller has cleared counts[2] on the stream already
+int hdf_launch_edge_flags(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, uint8_t* flags,
+                          unsigned long long* counts, bool counts_are_zero, hipStream_t st);
+int hdf_launch_surface_asd(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, void* ws,
+                           unsigned long long* result, uint32_t* hist_out, int64_t hist_len, hipStream_t st);

@@ -4,7 +4,8 @@ from ._lib import BF16, F32, EXPORTS, HdfError, LIB_PATH, lib  # noqa: F401
 _AUGMENT = ("TrainTransform2D", "TrainTransform3D", "augment_2d", "augment_3d", "crop_origin", "flip2d_code", "flip_flags",
             "rotate_degree", "rotate_matrix", "trz_matrix", "erase2d_keep", "gamma2d", "intensity_2d_", "label_bbox_2d",
             "noise2d_flag", "zoom2d_canvas", "zoom_2d", "crop_resize", "resize_3d", "trunc_normalize_")
-_SURFACE = ("cal_score", "multi_dice", "multi_hd", "multi_jc", "multi_vs", "surface_scores")
+_SURFACE = ("cal_score", "multi_dice", "multi_hd", "multi_jc", "multi_vs", "surface_scores",
+            "asd_from_result", "asd_scores", "cal_asd", "multi_asd")
 
 
 def __getattr__(name):

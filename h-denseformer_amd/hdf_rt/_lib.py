@@ -67,6 +67,9 @@ _PROTOS = {
     "hdf_op_mask_flags": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "hdf_op_edt_sq": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "hdf_surface_distances": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "hdf_surface_asd_workspace_bytes": (_i64, [_i, _i, _i]),
+    "hdf_op_edge_flags": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "hdf_surface_asd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
     "hdf_normalize_workspace_bytes": (_i64, [_i]),
     "hdf_normalize_mr": (_i, [_vp, _i, _i64, _vp, _vp]),
     "hdf_normalize_petct": (_i, [_vp, _i, _i64, _f, _f, _vp, _vp]),

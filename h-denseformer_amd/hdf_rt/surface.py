@@ -3,8 +3,13 @@ multi_jc, metrics.py:156-309).  The reference makes one SimpleITK pass per class
 signed Maurer distance maps, two label contours, a percentile over the surface distances.  Here a class is one
 hdf_surface_distances call (mask flags, two exact squared distance transforms, a histogram, a select: csrc/surface.hip)
 that leaves twelve integers on the device; all classes are enqueued, the rows come back in ONE copy and the floats are
-formed in fp64 on the host.  Definitions: include/hdf.h.  No CPU fallback."""
+formed in fp64 on the host.  Definitions: include/hdf.h.  No CPU fallback.
+
+The average surface distance (reference: cal_asd, multi_asd, utils.py:165-191, MONAI's SurfaceDistanceMetric on the host)
+is a call of its own, hdf_surface_asd (csrc/surface_asd.hip): MONAI's edge set and its distance to the other EDGE SET are
+not the contour and the Maurer map of cal_score.  It leaves four integers per class; the rest is the same."""
 import math
+import struct
 
 import numpy as np
 import torch
@@ -17,11 +22,16 @@ KEYS = ("Jaccard", "Dice", "VolumeSimilarity", "HausdorffDistance", "HausdorffDi
 # call on ITS stream (the kernels of two calls are ordered there); callers on two streams get one each and do not race.
 # About 9 bytes a voxel plus the histogram; nothing is evicted -- clear_workspaces() gives the memory back.
 _workspaces = {}
+# the same for hdf_surface_asd, which needs one histogram more: a cache of its own, so that neither call is ever handed
+# the other's allocation
+_asd_workspaces = {}
+ASD_KEYS = ("ASD", "ASD_pred_to_gt", "ASD_gt_to_pred")
 
 
 def clear_workspaces():
     """drop the cached workspaces (a caller that is done scoring, or moves on to another volume shape)"""
     _workspaces.clear()
+    _asd_workspaces.clear()
 
 
 def _volume(a, what):
@@ -37,14 +47,15 @@ def _volume(a, what):
     return a.to(torch.uint8).contiguous()
 
 
-def _workspace(dev, shape):
+def _workspace(dev, shape, cache=None, size_fn="hdf_surface_workspace_bytes"):
+    cache = _workspaces if cache is None else cache
     key = (str(dev), stream_ptr()) + shape
-    ws = _workspaces.get(key)
+    ws = cache.get(key)
     if ws is None:
-        n = lib().hdf_surface_workspace_bytes(*shape)
+        n = getattr(lib(), size_fn)(*shape)
         if n < 0:
-            raise _lib.HdfError("hdf_surface_workspace_bytes: " + lib().hdf_last_error().decode(errors="replace"))
-        ws = _workspaces[key] = torch.empty(n, dtype=torch.uint8, device=dev)
+            raise _lib.HdfError(size_fn + ": " + lib().hdf_last_error().decode(errors="replace"))
+        ws = cache[key] = torch.empty(n, dtype=torch.uint8, device=dev)
     return ws
 
 
@@ -63,15 +74,20 @@ def scores_from_result(row):
     return out
 
 
-def surface_scores(target, prediction, labels):
-    """one dict of KEYS per label in `labels` (each 1..255), for two uint8 volumes [D, H, W]"""
+def _pair(target, prediction):
+    """both volumes on the target's device, and their common shape"""
     tgt, prd = _volume(target, "target"), _volume(prediction, "prediction")
     if prd.device != tgt.device:
         prd = prd.to(tgt.device)
     if tgt.shape != prd.shape:
         raise ValueError(f"target {tuple(tgt.shape)} and prediction {tuple(prd.shape)} differ")
+    return tgt, prd, tuple(int(s) for s in tgt.shape)
+
+
+def surface_scores(target, prediction, labels):
+    """one dict of KEYS per label in `labels` (each 1..255), for two uint8 volumes [D, H, W]"""
+    tgt, prd, shape = _pair(target, prediction)
     labels = [int(k) for k in labels]
-    shape = tuple(int(s) for s in tgt.shape)
     with torch.cuda.device(tgt.device):
         ws = _workspace(tgt.device, shape)
         rows = torch.empty((max(len(labels), 1), 12), dtype=torch.int64, device=tgt.device)
@@ -109,3 +125,60 @@ def multi_vs(y_true, y_pred, num_classes):
 
 def multi_jc(y_true, y_pred, num_classes):
     return _multi("Jaccard", y_true, y_pred, num_classes)
+
+
+# ------------------------------------------------------------------------------------------- average surface distance
+def asd_from_result(row):
+    """the symmetric and the two directed average surface distances in fp64 from one result[4] row of hdf_surface_asd
+    (|E6(T)|, |E6(P)| and the bit patterns of the two sums).  Empty edge sets as MONAI's get_surface_distance treats them:
+    nothing to measure from is NaN, nothing to measure to is +inf."""
+    n_t, n_p, bits_a, bits_b = (int(v) for v in row)
+    sum_a, sum_b = (struct.unpack("<d", struct.pack("<Q", b & 0xFFFFFFFFFFFFFFFF))[0] for b in (bits_a, bits_b))
+    nan, inf = float("nan"), float("inf")
+
+    def directed(total, n_from, n_to):
+        return nan if n_from == 0 else inf if n_to == 0 else total / n_from
+
+    if n_t == 0 or n_p == 0:
+        sym = nan if n_t == n_p else inf
+    else:
+        sym = (sum_a + sum_b) / (n_p + n_t)         # the pooled mean, not the mean of the two means
+    return {"ASD": sym, "ASD_pred_to_gt": directed(sum_a, n_p, n_t), "ASD_gt_to_pred": directed(sum_b, n_t, n_p)}
+
+
+def asd_scores(target, prediction, labels):
+    """one dict of ASD_KEYS per label in `labels` (each 1..255), for two uint8 volumes [D, H, W]"""
+    tgt, prd, shape = _pair(target, prediction)
+    labels = [int(k) for k in labels]
+    with torch.cuda.device(tgt.device):
+        ws = _workspace(tgt.device, shape, _asd_workspaces, "hdf_surface_asd_workspace_bytes")
+        rows = torch.empty((max(len(labels), 1), 4), dtype=torch.int64, device=tgt.device)
+        for i, k in enumerate(labels):
+            check(lib().hdf_surface_asd(ptr(tgt), ptr(prd), k, *shape, ptr(ws), ws.numel(), ptr(rows[i]), None, 0,
+                                        stream_ptr()), "hdf_surface_asd")
+        host = rows.cpu()          # the one D2H copy, after every class is enqueued
+    return [asd_from_result(host[i].tolist()) for i in range(len(labels))]
+
+
+def _mask(a, what):
+    """a boolean or uint8 mask as [D, H, W], or in the reference's [1, 1, a, b, c] form (utils.py:180): 0 / 1 uint8"""
+    if not torch.is_tensor(a):
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    if a.dim() == 5 and a.shape[0] == 1 and a.shape[1] == 1:
+        a = a[0, 0]
+    return (_volume(a, what) != 0).to(torch.uint8)
+
+
+def cal_asd(predict, target):
+    """utils.cal_asd(predict, target) for one pair of boolean or uint8 masks (non-zero = inside), [D, H, W] or the
+    reference's [1, 1, a, b, c], numpy or torch, host or device: MONAI's symmetric average surface distance as a float"""
+    prd, tgt = _mask(predict, "predict"), _mask(target, "target")
+    return asd_scores(tgt, prd, [1])[0]["ASD"]
+
+
+def multi_asd(y_true, y_pred, num_classes):
+    """utils.multi_asd(y_true, y_pred, num_classes) for two label maps [D, H, W]: (per-class ASD rounded to 4 places,
+    their mean rounded likewise); an inf or a NaN goes through np.mean as it does in the reference.  The reference's
+    permute(1, 2, 0) only renames the axes (unit spacing): the maps are taken as they are."""
+    vals = [round(s["ASD"], 4) for s in asd_scores(y_true, y_pred, range(1, num_classes + 1))]
+    return vals, round(np.mean(vals), 4)

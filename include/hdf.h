@@ -298,6 +298,44 @@ int hdf_surface_distances(const uint8_t* target, const uint8_t* prediction, int 
                           void* workspace, int64_t workspace_bytes, uint64_t* result, uint32_t* histogram_out,
                           int64_t histogram_len, hdf_stream stream);
 
+/* ---- average surface distance of one class (utils.py:165-191, cal_asd and multi_asd; the reference calls MONAI's
+ * SurfaceDistanceMetric(symmetric=True) on the host).  T, P and the volume as above.  These definitions come from
+ * reading MONAI's source (get_mask_edges, get_surface_distance, compute_average_surface_distance), not from running it;
+ * what they are tested against is the sequence of scipy calls MONAI makes.  MONAI's surface and distance are not the
+ * ones of hdf_surface_distances, so ASD cannot be read off that call's results:
+ *   E6(M)  = the voxels of M with at least one of their six face neighbours not in M, where a neighbour outside the
+ *            volume is NOT in M: M ^ scipy.ndimage.binary_erosion(M) with the default structure and border_value = 0.
+ *            (MONAI crops to the bounding box of P | T first; outside that box there is no foreground, so nothing
+ *            changes.)  A depth-1 volume is all edge; a mask that fills the volume has the volume's shell as its edge;
+ *            E6(M) is empty only when M is; E6 and C6 differ exactly on the volume's faces.
+ *   dE_T(v) = the Euclidean distance from v to the nearest voxel of E6(T) (distance_transform_edt(~E6(T))), not to the
+ *            nearest voxel of T; its square d2_ET is an exact integer.  dE_P likewise.
+ *   A = { dE_T(v) : v in E6(P) } (prediction to ground truth), B = { dE_P(v) : v in E6(T) }.
+ *   ASD    = (sum A + sum B) / (|A| + |B|), the pooled mean (not the mean of the two means); the directed
+ *            sum A / |A| (symmetric=False) and sum B / |B| come with it.
+ *   Empty sets: E6(T) and E6(P) both empty -> NaN; exactly one empty -> +inf.  Directed, prediction to ground truth:
+ *            E6(P) empty -> NaN, E6(T) empty with E6(P) non-empty -> +inf; the other direction with the roles swapped.
+ * The reference's permute(1, 2, 0) ahead of the call only renames the axes: with unit spacing it changes nothing.
+ * hdf_op_edge_flags: flags[v] = 1 v in T | 2 v in P | 64 v in E6(T) | 128 v in E6(P) -- the two bits hdf_op_mask_flags
+ * leaves clear; bits 4..32 are 0 here.  counts[2] uint64 = |E6(T)| |E6(P)|.  hdf_op_edt_sq with seed_bit 64 / 128 gives
+ * d2_ET / d2_EP; it accepts a workspace of hdf_surface_asd_workspace_bytes, which is never below
+ * hdf_surface_workspace_bytes.
+ * hdf_surface_asd: result[4] uint64 = |E6(T)| |E6(P)| bits(sum A) bits(sum B), the sums as IEEE fp64 bit patterns:
+ * sum_k hist[k] sqrt((double)k) over the histogram of the squared distances, added in an order that depends on the
+ * volume's dimensions alone (no floating-point atomics: two calls on the same inputs agree in every bit; relative error
+ * below 5e-13).  Both sums are +0 when either edge set is empty; the caller forms NaN / +inf from the two counts.
+ * histogram_out (nullable, device): [2][histogram_len], row 0 the count of every squared distance in A, row 1 in B
+ * (entries past (D-1)^2 + (H-1)^2 + (W-1)^2 are 0); a row sums to |A| = |E6(P)| resp. |B| = |E6(T)| when neither edge set
+ * is empty and is all 0 otherwise.  Pointers, stream ordering, workspace reuse and refusals ("surface: ...", before
+ * anything is launched) as for hdf_surface_distances, with hdf_surface_asd_workspace_bytes(D, H, W) as the size (-1 for
+ * refused dimensions) and a negative histogram_len refused as well. */
+int64_t hdf_surface_asd_workspace_bytes(int D, int H, int W);
+int hdf_op_edge_flags(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
+                      uint8_t* flags, uint64_t* counts, hdf_stream stream);
+int hdf_surface_asd(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
+                    void* workspace, int64_t workspace_bytes, uint64_t* result, uint32_t* histogram_out,
+                    int64_t histogram_len, hdf_stream stream);
+
 /* ---- input normalisation on the device, in place on one fp32 sample [channels][voxels] -----------------------
  * hdf_normalize_mr: MRNormalize (data_utils/data_loader.py:39-50): every channel divided by its maximum when that is
  * non-zero, then negatives clamped to 0.  hdf_normalize_petct: PETandCTNormalize (:53-68): channel 0 ->
