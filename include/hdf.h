@@ -698,7 +698,9 @@ int hdf_op_attention_bwd(const float* qkv, const float* ob, const float* lse, co
 int hdf_op_attention_amp_bwd(int dtype, const float* qkv, const float* ob, const float* lse, const float* d_ob,
                              float* dqkv, int nseq, int N, hdf_stream stream);
 /* Dense_TransformerBlock front (:115-119,133-138): Conv3d(1 -> DM, k16, s16) + flatten + position embedding + dropout.
- * x: [B][M][D][H][W]; writes F[:, 0:DM].  backward: dF -> dweight, dpos (+=), dbias (+=); scratch rows*DM floats */
+ * x: [B][M][D][H][W]; writes F[:, 0:DM].  backward: dF -> dweight (+=), dpos (+=), dbias (+=): all three gradients are
+ * ACCUMULATED into what the buffers hold (hdf_backward zeroes the flat gradient buffer first), like every other
+ * parameter gradient of this section; scratch rows*DM floats */
 int hdf_op_patch_embed_fwd(const float* x, int M, int B, int D, int H, int W, int DM, const float* weight,
                            const float* bias, const float* pos, int64_t mstride, float* F, int training, uint64_t seed,
                            hdf_stream stream);
