@@ -555,6 +555,35 @@ int hdf_op_upsample_bwd(int dtype, const void* dout, int64_t dout_pitch, void* d
   return hdf_launch_upsample_bwd(dtype, CRows{dout, dout_pitch}, Rows{din, din_pitch}, Extent{N, C, Di, Hi, Wi},
                                  (hipStream_t)stream);
 }
+// The 2-D forms (models/HDenseFormer_2D.py:166-170, :194-202) of the four entries above, on depth-1 tensors: what the 2-D
+// plan launches (exec.hip: e.extent sets flat).  A pooled depth of 1 is a legitimate 3-D call, so the form is chosen by
+// the entry, not by the extent.
+int hdf_op_enc_tail_2d(int dtype, const void* y, int64_t y_pitch, const float* scale, const float* shift, const void* skip,
+                       int64_t skip_pitch, void* ds, int64_t ds_pitch, void* pooled, int64_t pooled_pitch, uint8_t* idx,
+                       int N, int C, int Ho, int Wo, hdf_stream stream) {
+  HDF_CHECK_ARG(y && scale && shift && skip && ds && pooled && idx, "enc_tail_2d: null argument");
+  return hdf_launch_enc_tail(dtype, CRows{y, y_pitch}, NormStats{scale, shift}, CRows{skip, skip_pitch}, Rows{ds, ds_pitch},
+                             Rows{pooled, pooled_pitch}, idx, Extent{N, C, 1, Ho, Wo, /*flat*/ 1}, (hipStream_t)stream);
+}
+int hdf_op_maxpool_bwd_in_2d(int dtype, const void* dout, int64_t dout_pitch, const uint8_t* idx, void* din,
+                             int64_t din_pitch, const void* y, int64_t y_pitch, const float* scale, const float* shift,
+                             const float* mean, const float* rstd, float* partials, int N, int C, int Ho, int Wo,
+                             hdf_stream stream) {
+  HDF_CHECK_ARG(dout && idx && din && y && scale && shift && mean && rstd && partials, "maxpool_bwd_in_2d: null argument");
+  return hdf_launch_maxpool_bwd_in(dtype, CRows{dout, dout_pitch}, idx, Rows{din, din_pitch}, CRows{y, y_pitch},
+                                   NormStats{scale, shift, mean, rstd}, partials, Extent{N, C, 1, Ho, Wo, /*flat*/ 1},
+                                   (hipStream_t)stream);
+}
+int hdf_op_upsample_fwd_2d(int dtype, const void* y, int64_t y_pitch, const float* scale, const float* shift, void* out,
+                           int64_t out_pitch, int N, int C, int Hi, int Wi, hdf_stream stream) {
+  return hdf_launch_upsample_fwd(dtype, CRows{y, y_pitch}, NormStats{scale, shift}, Rows{out, out_pitch},
+                                 Extent{N, C, 1, Hi, Wi, /*flat*/ 1}, (hipStream_t)stream);
+}
+int hdf_op_upsample_bwd_2d(int dtype, const void* dout, int64_t dout_pitch, void* din, int64_t din_pitch, int N, int C,
+                           int Hi, int Wi, hdf_stream stream) {
+  return hdf_launch_upsample_bwd(dtype, CRows{dout, dout_pitch}, Rows{din, din_pitch}, Extent{N, C, 1, Hi, Wi, /*flat*/ 1},
+                                 (hipStream_t)stream);
+}
 
 
 // ---- transformer / head operator level (HDenseFormer.py:47-145,223-227) -------------------------------------------

@@ -119,6 +119,10 @@ _PROTOS = {
     "hdf_op_maxpool_bwd": (_i, [_i, _vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "hdf_op_upsample_fwd": (_i, [_i, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "hdf_op_upsample_bwd": (_i, [_i, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "hdf_op_enc_tail_2d": (_i, [_i, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _vp]),
+    "hdf_op_maxpool_bwd_in_2d": (_i, [_i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "hdf_op_upsample_fwd_2d": (_i, [_i, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "hdf_op_upsample_bwd_2d": (_i, [_i, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
     "hdf_op_attention_fwd": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "hdf_op_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "hdf_op_attention_amp_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

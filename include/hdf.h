@@ -676,6 +676,29 @@ int hdf_op_upsample_fwd(int dtype, const void* y, int64_t y_pitch, const float* 
                         int64_t out_pitch, int N, int C, int Di, int Hi, int Wi, hdf_stream stream);
 int hdf_op_upsample_bwd(int dtype, const void* dout, int64_t dout_pitch, void* din, int64_t din_pitch, int N, int C,
                         int Di, int Hi, int Wi, hdf_stream stream);
+/* The 2-D forms of the four entries above, as the 2-D model's plan runs them, on depth-1 channels-last tensors
+ * [N][H][W][pitch].  A pooled depth of 1 is a legitimate call of the 3-D entries (a 2 x 2 x 2 window), so the 2-D form has
+ * entries of its own.  (Ho, Wo) / (Hi, Wi): the low-resolution side.
+ * hdf_op_enc_tail_2d: ds = relu(y * scale + shift) + skip, stored, and MaxPool2d(2) (models/HDenseFormer_2D.py:194-202)
+ * of the stored values with the arg-max byte per channel (0..3 = dy*2 + dx, first maximum in scan order as torch). */
+int hdf_op_enc_tail_2d(int dtype, const void* y, int64_t y_pitch, const float* scale, const float* shift, const void* skip,
+                       int64_t skip_pitch, void* ds, int64_t ds_pitch, void* pooled, int64_t pooled_pitch, uint8_t* idx,
+                       int N, int C, int Ho, int Wo, hdf_stream stream);
+/* MaxPool2d(2) backward (models/HDenseFormer_2D.py:194-202) accumulated into din, with the first pass of the
+ * InstanceNorm(+ReLU) backward as in hdf_op_maxpool_bwd_in: partials[n][row][c][2] = (sum g, sum g * (y - mean) * rstd), g =
+ * the stored din where y * scale + shift is positive, hdf_op_maxpool_bwd_in_rows(C, 1, Ho, Wo) rows per sample. */
+int hdf_op_maxpool_bwd_in_2d(int dtype, const void* dout, int64_t dout_pitch, const uint8_t* idx, void* din,
+                             int64_t din_pitch, const void* y, int64_t y_pitch, const float* scale, const float* shift,
+                             const float* mean, const float* rstd, float* partials, int N, int C, int Ho, int Wo,
+                             hdf_stream stream);
+/* out [N][2 Hi][2 Wi] = F.interpolate(relu(y * scale + shift), scale_factor=2, mode='bilinear', align_corners=False)
+ * (models/HDenseFormer_2D.py:166-170); scale / shift [N][C] are required. */
+int hdf_op_upsample_fwd_2d(int dtype, const void* y, int64_t y_pitch, const float* scale, const float* shift, void* out,
+                           int64_t out_pitch, int N, int C, int Hi, int Wi, hdf_stream stream);
+/* din [N][Hi][Wi] = the adjoint of that bilinear x2 (models/HDenseFormer_2D.py:166-170 backward) applied to
+ * dout [N][2 Hi][2 Wi]: 4 x 4 taps per low-resolution element. */
+int hdf_op_upsample_bwd_2d(int dtype, const void* dout, int64_t dout_pitch, void* din, int64_t din_pitch, int N, int C,
+                           int Hi, int Wi, hdf_stream stream);
 
 
 /* ---- operator level, transformer branch and heads (what nn.Linear / LayerNorm / GELU / Softmax / matmul / Dropout and

@@ -39,6 +39,8 @@ route -> case (every case for bf16 and float16; "+f32" where fp32 storage runs t
   hdf_op_norm_relu_add, enc_tail(_up)       test_norm_relu_add, test_encoder_tail, test_encoder_tail_up   +f32
   hdf_op_upsample_fwd / _bwd                test_upsample                                     +f32
   hdf_op_maxpool_bwd, accumulate = 1        test_maxpool_backward_accumulate                  +f32
+  2-D pool family (hdf_op_enc_tail_2d, _maxpool_bwd_in_2d, _upsample_fwd_2d / _bwd_2d) and hdf_op_in_finalize
+                                            tests/test_gpu_pool2d_rounding.py                 +f32
   hdf_op_head_fwd / _bwd                    test_head                                         +f32
   hdf_op_block_out_fwd, attnall             test_block_out_attnall
 Each check prints one line "ROUNDING <case> <worst error / bound>" (pytest -s shows them)."""
