@@ -119,7 +119,7 @@ int transformer_forward(Exec& e, const float* x) {
   // (flat: the 2-D input itself, depth 1, against depth slice 0 of the embedded 16^3 patch kernel)
   HDF_TRY(tf_patch_embed_fwd(d, x, p->flat ? 1 : p->D, p->H, p->W, pm + p->pe_w, pm + p->pe_b, pm + p->pe_pos, F0,
                              e.st, PE_LP, p->flat ? 1 : 16));
-  if (p->tf_fwd_chain) {  // all layers of all blocks in one persistent launch (transformer_chain.hip)
+  if (p->tf_fwd_chain) {  // all layers of all blocks in one persistent launch (tf_chain_fwd.hip)
     if (e.tf_packed) HDF_TRY(e.wait(e.st, e.tf_packed, "the transformer's stream behind the weight packs"));
     return tf_chain_forward(d, p->tf_cp, p->nb, pm, F0, e.f(p->tf_save), e.at(p->attnall),
                             reinterpret_cast<unsigned*>(e.ws + p->tf_sync), e.ws + p->tf_wpack, e.f(p->tf_frag), p->dtype, e.st,
@@ -192,7 +192,7 @@ int transformer_backward(Exec& e, const float* x) {
   };
   p->tf_bwd_chain = p->tf_fwd_chain && tf_chain_backward_supported(d, p->dtype);
   if (p->tf_bwd_chain) {
-    // one persistent launch for all layers (transformer_chain.hip); then every block's weight-matrix gradients from the
+    // one persistent launch for all layers (tf_chain_bwd.hip); then every block's weight-matrix gradients from the
     // tapes on the side stream, next to the patch embedding's backward on this one
     HDF_TRY(tf_chain_backward(d, p->tf_cp, p->nb, pm, e.grads, F0, e.f(p->tf_save), dF, e.at(p->dAttnall),
                               e.f(p->tf_tape), e.f(p->tf_otape), scratch, e.f(p->tf_frag), e.ws + p->tf_wpack,
@@ -250,7 +250,7 @@ int transformer_backward(Exec& e, const float* x) {
 
 }  // namespace hdf_internal
 
-// A persistent transformer launch that gave up (transformer_chain.hip: chain_wait) leaves 1 + a workgroup id in its timeout
+// A persistent transformer launch that gave up (tf_chain.h: chain_wait) leaves 1 + a workgroup id in its timeout
 // word.  NaN written into the branch output does NOT survive the network -- relu(InstanceNorm(.)) is fmaxf(x * scale +
 // shift, 0), and fmaxf returns the operand that is not NaN -- so the step would end with finite, plausible-looking logits
 // and gradients.  These two launches (one workgroup each, the LAST launch of a forward / of a backward on the caller's

@@ -107,7 +107,7 @@ struct hdf_plan {
   View xin, attnall, attnout, at[3] /*at[k] lives at level k*/, cat[3], pooled[3], x4;
   size_t pool_idx[3];
   size_t tf_F, tf_save, tf_scratch, tf_dF, tf_tape = 0, tf_otape = 0;
-  size_t tf_sync = 0;   // arrival counters of the persistent transformer kernels (transformer_chain.hip)
+  size_t tf_sync = 0;   // arrival counters of the persistent transformer kernels (tf_chain.h)
   size_t tf_frag = 0;   // operand records the forward leaves for the attention backward (16-bit modes)
   size_t tf_wpack = 0;  // fragment-major copies of the dense layers' weight matrices for those kernels
   size_t stat_partials, wgrad_ws, inb_partials, inb_k;
@@ -130,7 +130,7 @@ struct hdf_plan {
   hipEvent_t bucket_ev[HDF_NUM_GRAD_BUCKETS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   // hdf_plan_set_probe: caller-owned events recorded around the dominant conv launch of the forward (measurement only)
   hipEvent_t probe_start = nullptr, probe_stop = nullptr;
-  // Persistent transformer kernels (transformer_chain.hip).  chain_flag: one host-mapped word a launch writes (system
+  // Persistent transformer kernels (tf_chain.h: chain_wait).  chain_flag: one host-mapped word a launch writes (system
   // scope) when one of its per-sequence barriers gives up; read by the next forward / backward call of the plan without
   // synchronising (chain_flag_check).  chain_off: sticky -- after a give-up the plan runs the launch chain.
   // tf_fwd_chain: which arrangement the LAST forward ran; its backward follows it (the operand records and the

@@ -1,5 +1,5 @@
 // Token-tile helpers shared by the fused token kernels (transformer_fused.hip) and the persistent chain kernels
-// (transformer_chain.hip): GEMM fragments on v_mfma_f32_16x16x4_f32, LayerNorm(32) forward / backward pieces, tapes.
+// (tf_chain_fwd.hip, tf_chain_bwd.hip): GEMM fragments on v_mfma_f32_16x16x4_f32, LayerNorm(32) forward / backward pieces, tapes.
 // See the head of transformer_fused.hip for the GEMM form.  Thread maps assume the FIRST 256 threads of a workgroup.
 #pragma once
 #include "transformer.h"
@@ -8,23 +8,24 @@ namespace tftok {
 
 constexpr int TT = 16;  // tokens per workgroup
 constexpr int LD32 = 36, LD64 = 68;  // LDS row pitches (floats) of the 32- and 64-wide token tiles
-constexpr size_t LDS_LIMIT_F = 160 * 1024;
 
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-
-struct DropF {
-  int training;
-  uint32_t seed, thresh;
-  float scale;
-  __device__ __forceinline__ float mask(uint32_t site, uint32_t idx) const {
-    if (!training) return 1.f;
-    return hdf_keep(hdf_site_key(seed, site), idx, thresh) ? scale : 0.f;
-  }
-};
 
 __device__ __forceinline__ f32x4 zero4() {
   f32x4 z = {0.f, 0.f, 0.f, 0.f};
   return z;
+}
+// four K = 4 steps of the f32 MFMA: acc += A[16][16] * B[16][16], this lane's four A values in `a`, its four B values in
+// `w` (always in this order: every GEMM of the token stages must add its products in the same order wherever it runs)
+__device__ __forceinline__ f32x4 mma4(f32x4 acc, const float4& a, const float4& w) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w.z, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w.w, acc, 0, 0, 0);
+  return acc;
+}
+__device__ __forceinline__ f32x4 mma4(f32x4 acc, const float4& a, const float* w) {
+  return mma4(acc, a, make_float4(w[0], w[1], w[2], w[3]));
 }
 
 // per-lane weight fragment: NF4 float4 = this lane's (sub-)quarter of weight row n (lane & 15) of a 16-row tile
@@ -49,10 +50,7 @@ __device__ __forceinline__ void wmma(f32x4& acc, const WFrag<NF4>& f, const floa
   for (int j = 0; j < NF4; j++) {
     if (j < n4) {
       const float4 a = pa[j];
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, f.v[j].x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, f.v[j].y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, f.v[j].z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, f.v[j].w, acc, 0, 0, 0);
+      acc = mma4(acc, a, f.v[j]);
     }
   }
 }
@@ -74,10 +72,7 @@ __device__ __forceinline__ void wmma_stream(f32x4& acc, const float* __restrict_
     for (int j = 0; j < 4; j++) {
       if (c + j < n4) {
         const float4 a = pa[c + j];
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[j].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[j].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[j].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[j].w, acc, 0, 0, 0);
+        acc = mma4(acc, a, w[j]);
       }
     }
 #pragma unroll
@@ -96,7 +91,7 @@ __device__ __forceinline__ LnP ln_load(const float* __restrict__ gam, const floa
   return LnP{gam[c], gam[c + 1], bet[c], bet[c + 1]};
 }
 // (every sum of products in these helpers is an explicit fma under contract(off): the token kernels of
-// transformer_fused.hip and the persistent kernels of transformer_chain.hip must round identically, and left to the
+// transformer_fused.hip and the persistent kernels of tf_chain_*.hip must round identically, and left to the
 // compiler `d0 * d0 + d1 * d1` was an fma in one file and two multiplies + an add -- SLP-vectorised -- in the other)
 __device__ __forceinline__ void ln32(const float* sIn, float* sOut, const LnP& p) {
 #pragma clang fp contract(off)
@@ -145,10 +140,7 @@ __device__ __forceinline__ void cmma(f32x4& acc, const CFrag<NS>& f, const float
   for (int j = 0; j < NS / 4; j++) {
     if (4 * j < ns) {
       const float4 a = pa[j];
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, f.v[4 * j + 0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, f.v[4 * j + 1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, f.v[4 * j + 2], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, f.v[4 * j + 3], acc, 0, 0, 0);
+      acc = mma4(acc, a, f.v + 4 * j);
     }
   }
 }
@@ -166,10 +158,7 @@ __device__ __forceinline__ void cmma_stream(f32x4& acc, const float* __restrict_
     for (int j = 0; j < 2; j++) {
       if (c + 4 * j < OQ) {
         const float4 a = pa[(c >> 2) + j];
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[4 * j + 0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[4 * j + 1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[4 * j + 2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[4 * j + 3], acc, 0, 0, 0);
+        acc = mma4(acc, a, w + 4 * j);
       }
     }
   }

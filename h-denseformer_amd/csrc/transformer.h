@@ -8,10 +8,35 @@
 
 // delta of the attention backward: (dO . ob) over the 4 components of a head.  One explicit fma chain under contract(off):
 // as a plain sum of four products its rounding depended on how the surrounding code was vectorised, and the persistent
-// backward kernel (transformer_chain.hip) must reproduce the attention backward kernels bit for bit.
+// backward kernel (tf_chain_bwd.hip) must reproduce the attention backward kernels bit for bit.
 __device__ __forceinline__ float tf_dot4(const float4& a, const float4& b) {
 #pragma clang fp contract(off)
   return __builtin_fmaf(a.w, b.w, __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x)));
+}
+
+// dropout mask of one element (TfDims: seed, thresh24, keep_scale): keep_scale or 0 in training, 1 otherwise
+struct DropF {
+  int training;
+  uint32_t seed, thresh;
+  float scale;
+  __device__ __forceinline__ float mask(uint32_t site, uint32_t idx) const {
+    if (!training) return 1.f;
+    return hdf_keep(hdf_site_key(seed, site), idx, thresh) ? scale : 0.f;
+  }
+};
+
+// dynamic LDS a transformer kernel may ask for; above 64 KB it has to be opted into per kernel (once)
+constexpr size_t LDS_LIMIT = 160 * 1024;
+template <typename Kern>
+int allow_lds(Kern kern, size_t bytes) {
+  if (bytes <= 64 * 1024) return HDF_OK;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)LDS_LIMIT);
+  if (e != hipSuccess) {
+    hdf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+    return HDF_ERR_HIP;
+  }
+  return HDF_OK;
 }
 
 struct TfDims {
@@ -161,7 +186,8 @@ struct TfTokenBwd {
 };
 int tf_token_bwd(const TfDims& d, const TfTokenBwd& t, int dtype, hipStream_t st);
 
-// ---- persistent chain kernels (transformer_chain.hip): every dense layer of every block in ONE launch per direction.
+// ---- persistent chain kernels (tf_chain_fwd.hip, tf_chain_bwd.hip; sizes, predicates and the weight pack:
+// tf_chain_host.hip): every dense layer of every block in ONE launch per direction.
 // Parameter addressing of a branch: tensor k of layer l of block b sits at blk0 + b * blk_stride + loff[l][k] floats from the
 // flat parameter (or gradient) buffer's base, + m * mstride for modality m.  loff order = the members of TfLayerP;
 // ooff = the block's out_layer (wa, ba, wb, bb).

@@ -11,22 +11,9 @@
 // host-side entry points.  Everything of a dense layer between two attention launches lives in
 // transformer_fused.hip (tok_fwd_kernel / tok_bwd_kernel / tf_wgrad_kernel); the round-1 VALU token kernels
 // (dense_pre/post_*, block_out_*) were removed in round 3.
-#include "transformer.h"
+#include "tf_attn.h"
 
 namespace {
-
-constexpr size_t LDS_LIMIT = 160 * 1024;
-
-struct Drop {
-  int training;
-  uint32_t seed, thresh;
-  float scale;
-  __device__ __forceinline__ float mask(uint32_t site, uint32_t idx) const {
-    if (!training) return 1.f;
-    return hdf_keep(hdf_site_key(seed, site), idx, thresh) ? scale : 0.f;
-  }
-};
-__device__ __forceinline__ Drop make_drop(const TfDims& d) { return Drop{d.training, d.seed, d.thresh24, d.keep_scale}; }
 
 // ------------------------------------------------------------------------------ K2: attention
 // grid (ceil(N/AQ), 8 heads, M*B).  QL lanes per query, keys interleaved over the QL lanes.  The pair loops are
@@ -34,12 +21,8 @@ __device__ __forceinline__ Drop make_drop(const TfDims& d) { return Drop{d.train
 // (v_pk_mul/fma_f32), the exponentials are raw v_exp_f32 on scores pre-scaled by log2(e) (folded into the 0.5
 // query scale), and the LDS arrays are padded to whole trips so that only the fwd/dQ tail trip carries a mask
 // (dK/dV pads with lse = +inf: the probability of a padded query is exp2(-inf) = 0).
-constexpr int QL = 4, AQ = 256 / QL, AU = 4, ATRIP = QL * AU;
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 lo2(const float4& v) { return f2{v.x, v.y}; }
-__device__ __forceinline__ f2 hi2(const float4& v) { return f2{v.z, v.w}; }
-__host__ __device__ inline int attn_rows(int N) { return (N + ATRIP - 1) / ATRIP * ATRIP; }
+constexpr int QL = 4, AQ = 256 / QL, AU = 4;
+static_assert(QL * AU == ATRIP, "a trip = QL lanes x AU keys (tf_attn.h)");
 
 // K and V rows of one (sequence, head) -> LDS, padded rows zero; 4 row pairs in flight per thread
 __device__ __forceinline__ void attn_stage_kv(int N, int NP, const float* __restrict__ qkv, int64_t rowbase, int head,
@@ -86,7 +69,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(int N, const float* __res
   // Every sum of two products below is written as an explicit fma of one product into the other and contraction is
   // switched off: left to the compiler, `l * ca + l2 * cb` became fma(l, ca, l2 * cb) in one merge round and two
   // multiplies + an add in the next (SLP-vectorised products), i.e. the rounding depended on the surrounding code -- and
-  // the persistent kernel of transformer_chain.hip must reproduce this kernel bit for bit.
+  // the persistent kernel of tf_chain_fwd.hip must reproduce this kernel bit for bit.
 #pragma clang fp contract(off)
   HDF_CHAIN_PRIO();
   extern __shared__ float4 skv[];
@@ -148,6 +131,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(int N, const float* __res
   }
   if (j0 < NP) trip(j0, cur, std::true_type{});
   // merge the 4 key subsets of a query (lanes q, q + 16, q + 32, q + 48)
+  // (same text in tf_chain_fwd.hip: as one shared function it changed tf_chain_fwd_kernel's instruction order)
 #pragma unroll
   for (int off = 16; off < 64; off <<= 1) {
     const float m2 = __shfl_xor(mx, off, 64), l2 = __shfl_xor(l, off, 64);
@@ -180,26 +164,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(int N, const float* __res
 // The forward keeps the exact kernel in every mode: the same construction for P.V needs the row maximum before the first
 // accumulation (the result tile has the query on the register index, which a running maximum cannot rescale), i.e. a
 // second pass over the keys, and measured no faster (11.9 us against 11.5: the launch is bound by its prologue, not its
-// 32-trip loop) -- so the forward output is exact and only the gradient sees the 16-bit operands.
-template <int LP>
-struct LpPack;
-template <>
-struct LpPack<1> {  // bf16
-  static __device__ __forceinline__ uint16_t one(float v) { return f2bf(v); }
-  static __device__ __forceinline__ u32x2 four(float a, float b, float c, float d) { return u32x2{pack_bf2(a, b), pack_bf2(c, d)}; }
-  static __device__ __forceinline__ f32x4 mma(const u32x2& a, const u32x2& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
-  }
-};
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-template <>
-struct LpPack<2> {  // f16
-  static __device__ __forceinline__ uint16_t one(float v) { return f2h(v); }
-  static __device__ __forceinline__ u32x2 four(float a, float b, float c, float d) { return u32x2{pack_h2(a, b), pack_h2(c, d)}; }
-  static __device__ __forceinline__ f32x4 mma(const u32x2& a, const u32x2& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4, a), __builtin_bit_cast(f16x4, b), c, 0, 0, 0);
-  }
-};
+// 32-trip loop) -- so the forward output is exact and only the gradient sees the 16-bit operands.  (Packing and matrix
+// instruction per mode: LpPack, tf_attn.h.)
 // dQ: same decomposition as forward; the two 16 x 16 x 4 products per block (scores K.Q and T = V.dO) on the matrix core
 __device__ __forceinline__ void attn_bwd_dq_body(int N, int seq, const float* __restrict__ qkv,
                                                  const float* __restrict__ ob, const float* __restrict__ lse,
@@ -653,7 +619,7 @@ __global__ __launch_bounds__(256) void patch_embed_fwd2_kernel(TfDims d, const f
 #pragma unroll
       for (int i = 0; i < 4; i++) red[wave][mt * 16 + 4 * g + i][nt * 16 + i16] = acc[mt][nt][i];
   __syncthreads();
-  const Drop dr = make_drop(d);
+  const DropF dr{d.training, d.seed, d.thresh24, d.keep_scale};
   const uint32_t site = hdf_site_id(m, 63, 7, 7);
   const int cl = threadIdx.x & 63, col = col0 + cl;
   const float bias = bpe[(int64_t)m * d.mstride + col];
@@ -673,7 +639,7 @@ __global__ __launch_bounds__(256) void patch_embed_fwd2_kernel(TfDims d, const f
 __global__ void patch_embed_bwd_prep_kernel(TfDims d, const float* __restrict__ dF, float* __restrict__ dtok,
                                             float* __restrict__ dbpe, float* __restrict__ dpos) {
   const int m = blockIdx.y, DM = d.DM, BN = d.B * d.N;
-  const Drop dr = make_drop(d);
+  const DropF dr{d.training, d.seed, d.thresh24, d.keep_scale};
   const uint32_t site = hdf_site_id(m, 63, 7, 7);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < d.N * DM; i += gridDim.x * blockDim.x) {
     int n = i / DM, c = i - n * DM;
@@ -773,19 +739,6 @@ __global__ __launch_bounds__(256) void patch_embed_wgrad_kernel(TfDims d, const 
         *q += acc[i];
     }
   }
-}
-
-// dynamic LDS above 64 KB has to be opted into per kernel (once)
-template <typename Kern>
-int allow_lds(Kern kern, size_t bytes) {
-  if (bytes <= 64 * 1024) return HDF_OK;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)LDS_LIMIT);
-  if (e != hipSuccess) {
-    hdf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
-    return HDF_ERR_HIP;
-  }
-  return HDF_OK;
 }
 
 }  // namespace

@@ -626,24 +626,12 @@ __global__ __launch_bounds__(256) void tok_bwd_kernel(TokBwd a) {
   }
 }
 
-template <typename Kern>
-int allow_lds_f(Kern kern, size_t bytes) {
-  if (bytes <= 64 * 1024) return HDF_OK;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)LDS_LIMIT_F);
-  if (e != hipSuccess) {
-    hdf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
-    return HDF_ERR_HIP;
-  }
-  return HDF_OK;
-}
-
 template <bool POST, bool OUT, bool PRE, typename T>
 int launch_tok_fwd(const TokFwd& a, hipStream_t st) {
   const TfDims& d = a.d;
   dim3 grid(ceil_div(d.B * d.N, TT), d.M);
   const size_t shm = (size_t)(TT * (d.DMF + 4) + 2 * TT * LD32 + TT * LD64 + 2 * 16 * 16) * sizeof(float);
-  HDF_TRY(allow_lds_f(tok_fwd_kernel<POST, OUT, PRE, T>, shm));
+  HDF_TRY(allow_lds(tok_fwd_kernel<POST, OUT, PRE, T>, shm));
   hipLaunchKernelGGL((tok_fwd_kernel<POST, OUT, PRE, T>), grid, dim3(256), shm, st, a);
   HDF_LAUNCH_CHECK();
   return HDF_OK;
@@ -750,7 +738,7 @@ int launch_tok_bwd(const TokBwd& a, hipStream_t st) {
   // of the level-0 data-gradient conv (conv_ws2<32,64>), i.e. on every CU during the level-0 encoder backward.
   const size_t shm = (size_t)(TT * ((OUTB ? d.DMF : d.DMF - 32) + 4) + (OUTB ? TT * (d.DM + 4) : 0) + TT * 100 +
                               7 * TT * LD32 + 2 * TT * LD64 + 2 * 16 * 16) * sizeof(float);
-  HDF_TRY(allow_lds_f(tok_bwd_kernel<PREB, OUTB, POSTB, T>, shm));
+  HDF_TRY(allow_lds(tok_bwd_kernel<PREB, OUTB, POSTB, T>, shm));
   hipLaunchKernelGGL((tok_bwd_kernel<PREB, OUTB, POSTB, T>), grid, dim3(256), shm, st, a);
   HDF_LAUNCH_CHECK();
   return HDF_OK;

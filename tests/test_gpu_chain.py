@@ -1,5 +1,5 @@
-"""The persistent transformer kernels (csrc/transformer_chain.hip: every dense layer of every block in one launch per
-direction, per-sequence barriers) against the launch chain they replace (tok_fwd / attention / tok_bwd ..., selected with
+"""The persistent transformer kernels (csrc/tf_chain_fwd.hip, tf_chain_bwd.hip: every dense layer of every block in one
+launch per direction, per-sequence barriers) against the launch chain they replace (tok_fwd / attention / tok_bwd ..., selected with
 HDF_NO_TF_CHAIN=1): the same fp32 operations in the same order, so every saved tensor of the branches
 (HDenseFormer.py:78-145: h0, q|k|v, attention output, log-sum-exp, h1, h2, the feature buffers), the four outputs and --
 in backward -- every gradient must agree BIT FOR BIT, and no per-sequence barrier may have timed out."""

@@ -10,7 +10,7 @@ UpConv chain) leaves g.attnall, the upstream gradient of the branches; stages = 
 plan.hip:hdf_plan_layout gives every one of these regions a range of its own in the arena (a bump allocator, nothing is
 reused), tf_F / tf_save / attnall are read before the backward starts, and g.attnall is read between the two backward calls
 AND after the second (asserted equal: the transformer backward only reads it).  What a training step runs is what is
-checked: the default arrangement (the two persistent kernels of transformer_chain.hip where the shape allows), the
+checked: the default arrangement (the two persistent kernels of tf_chain_fwd.hip / tf_chain_bwd.hip where the shape allows), the
 16-bit patch embedding and attention backward of the 16-bit plans, tf_wgrad over the tapes, the depth-1 patch embedding of
 the 2-D model with its token-chunked float-atomic weight gradient (tf_patch_embed_bwd: kblocks = 2, tchunks = max(1,
 min(ceil(B N / 256), 512 / (kblocks * ceil(DM / 32) * M))) = min(2, 32) = 2 at 256 x 256, batch 2, n_filters 16, 2
