@@ -27,13 +27,13 @@ __global__ void optim_prologue_kernel(OptimCtl* __restrict__ ctl, const float* _
   const int step = ctl->step + (skip ? 0 : 1);
   ctl->step = step;
   ctl->skip = skip ? 1 : 0;
-  // the host computes these as 1.f - powf(b, step) and sqrtf(.) (hdf_adam_step).  Double pow / sqrt rounded once to
-  // fp32 are the correctly rounded values; glibc's powf is that at all but a few steps (for these betas 5 of the first
-  // 3000, the first at step 685), so over a long run the two entries may differ by 1 ulp of a bias correction
-  const float bc1 = 1.f - (float)pow((double)b1, (double)step);
-  const float bc2 = 1.f - (float)pow((double)b2, (double)step);
-  ctl->bc1 = bc1;
-  ctl->bc2s = (float)sqrt((double)bc2);
+  // 1 - b^step and sqrt(1 - b2^step) of the fp32 betas, formed in double and rounded to fp32 ONCE, at the end.  The power
+  // must not be rounded before the subtraction: 1 - b2^k is about k * 1e-3 in the first steps, and a power rounded to
+  // fp32 leaves its 2^-25 there as up to 3.3e-6 of sqrt(1 - b2^k) (step 2), 200 times the final rounding.  The host forms
+  // the same two expressions for hdf_adam_step (hdf_launch_adam); both pows are within an ulp of a double, so the two
+  // entries agree unless 1 - b^k lies that close to the middle of two fp32 values
+  ctl->bc1 = (float)(1.0 - pow((double)b1, (double)step));
+  ctl->bc2s = (float)sqrt(1.0 - pow((double)b2, (double)step));
   ctl->gdiv = grad_scale ? *grad_scale : 1.f;
 }
 
@@ -145,8 +145,9 @@ int hdf_launch_optim(int rule, float* p, const float* g, float* s1, float* s2, c
 
 int hdf_launch_adam(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float b1,
                     float b2, float eps, float wd, int step, float gscale, hipStream_t st) {
-  float bc1 = 1.f - powf(b1, (float)step);
-  float bc2s = sqrtf(1.f - powf(b2, (float)step));
+  // as optim_prologue_kernel: in double, rounded to fp32 once
+  float bc1 = (float)(1.0 - pow((double)b1, (double)step));
+  float bc2s = (float)sqrt(1.0 - pow((double)b2, (double)step));
   unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(n, 256), 4096);
   hipLaunchKernelGGL(adam_kernel, dim3(gx), dim3(256), 0, st, p, g, m, v, decay, n, lr, b1, b2, eps, wd, bc1, bc2s,
                      gscale);

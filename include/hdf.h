@@ -520,7 +520,13 @@ int hdf_resize_3d(const float* image, const uint8_t* labels, int channels, int n
  * in fp32 too).  Refused with a "trunc_normalize:" message: a null image, n < 1, hi <= lo, a value that is not finite. */
 int hdf_trunc_normalize(float* image, int64_t n, float lo, float hi, hdf_stream stream);
 
-/* ---- optimizer: torch.optim.Adam as configured by trainer.py:793-840 (L2 weight decay on the mask) ---- */
+/* ---- optimizer: torch.optim.Adam as configured by trainer.py:793-840 (L2 weight decay on the mask) ----
+ * decay_mask may be null (no decay anywhere); grad_scale MULTIPLIES the gradient; step is 1-based.
+ * The betas are taken at their fp32 values: the bias corrections 1 - beta1^step and sqrt(1 - beta2^step) are formed from
+ * them in double and rounded to fp32 once.  torch forms its corrections from the Python doubles; for beta2 = 0.999 (0.999f
+ * is 1.29e-8 above it) its sqrt(1 - beta2^step) lies 6.4e-6 (relative) from this entry's in the first steps, 6.1e-6 at
+ * step 100 and still 1e-6 at step 3000, and every update differs by that factor (tests/test_optim_ref_cpu.py holds the
+ * figures). */
 int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   float grad_scale, hdf_stream stream);
@@ -532,7 +538,13 @@ int hdf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
  * initialised to the gradient by the first step; nesterov != 0: g + momentum*buf).
  * state1 / state2: exp_avg / exp_avg_sq, or the momentum buffer / null for SGD; beta1 is the momentum of SGD (beta2 and
  * eps unused).  Two parameter groups chosen by the decay_mask byte: lr_decay / wd_decay where it is set, lr_rest /
- * wd_rest elsewhere.  The gradient used is g * grad_mul / *grad_scale.
+ * wd_rest elsewhere.  The gradient used is g * grad_mul / *grad_scale.  SGD's step 1 (word 0 of step_state at 0) REPLACES
+ * the momentum buffer by the gradient, whatever the buffer held.
+ * Every hyper-parameter is taken at its fp32 value.  The bias corrections 1 - beta1^step and sqrt(1 - beta2^step) are
+ * formed from the fp32 betas in double and rounded to fp32 once.  torch forms its corrections from the Python doubles; for
+ * beta2 = 0.999 (0.999f is 1.29e-8 above it) its sqrt(1 - beta2^step) lies 6.4e-6 (relative) from this entry's in the first
+ * steps, 6.1e-6 at step 100 and still 1e-6 at step 3000, and every Adam / AdamW update differs by that factor
+ * (tests/test_optim_ref_cpu.py holds the figures; tests/optim_ref.py is the fp64 statement of the three rules).
  * grad_scale, found_inf (each may be null): DEVICE pointers to one fp32, the protocol of torch.amp.GradScaler for
  * optimizers that unscale inside their step.  *found_inf != 0: the call leaves parameters, state buffers and the step
  * counter bit for bit untouched.

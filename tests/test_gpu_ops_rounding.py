@@ -43,6 +43,7 @@ route -> case (every case for bf16 and float16; "+f32" where fp32 storage runs t
                                             tests/test_gpu_pool2d_rounding.py                 +f32
   hdf_op_head_fwd / _bwd                    test_head                                         +f32
   hdf_op_block_out_fwd, attnall             test_block_out_attnall
+  hdf_optim_step, hdf_adam_step, Flat*      tests/test_gpu_optim_rounding.py (fp32 only; bound: tests/optim_ref.py)
 Each check prints one line "ROUNDING <case> <worst error / bound>" (pytest -s shows them)."""
 import ctypes as C
 

@@ -6,7 +6,11 @@ synchronisation, and the state_dict round trip.
 The parity gate, 1e-5 on the worst per-tensor max|a-b| / max|b|, is the project's Adam gate
 (test_gpu_model.py::test_flat_adam_matches_torch_adam).  torch's fp32 optimizers against their own fp64 run on the same
 inputs over 8 steps differ by 3.2e-7 (SGD), 5.6e-7 (AdamW) and 3.1e-7 (Adam): the gate leaves about 17x over the
-reference's own rounding."""
+reference's own rounding.  What it can see is a step that is grossly wrong (a missing update, a wrong sign, the bias
+correction of another step, Adam's L2 decay gone: 1.2e-5).  What it cannot: at lr 1e-3 and weight_decay 1e-4 a dropped or
+inverted weight decay moves the gated number by 1.6e-6 at the most, and the two groups share one lr, so a swapped group is
+no change at all.  The arithmetic itself -- every element, both groups with their own lr and wd, grad_mul, loss scales,
+every step count and length -- is held to fp64 in tests/test_gpu_optim_rounding.py."""
 import numpy as np
 import pytest
 import torch
