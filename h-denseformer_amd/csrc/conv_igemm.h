@@ -3,7 +3,8 @@
 //   conv_s2.hip     the specialised stride-2 kernels hdf_launch_conv routes to
 //   conv_wr.hip     weights-in-registers form of the stride-1 launches
 //   conv_first.hip  the encoder's first layer and its weight gradient
-//   conv_wgrad.hip  weight gradients
+//   conv_wgrad.hip  weight gradients: hdf_launch_wgrad (routing, workspace size), the generic kernel, the slab reductions
+//   conv_wgrad2.hip, conv_wgrad_s2.hip  the specialised 16-bit weight-gradient kernels hdf_launch_wgrad routes to
 //   conv_pack.hip   weight packers
 #pragma once
 #include "hdf_common.h"
@@ -133,11 +134,20 @@ int hdf_launch_wgrad_first(int dtype, const void* dy, int64_t dy_pitch, int Cout
                            int N, int D, int H, int W, float* dw, int accumulate, void* workspace, size_t workspace_bytes,
                            hipStream_t st, const WgradFirstIn* in_bwd = nullptr);
 
-// ---- conv_wgrad.hip
+// ---- conv_wgrad.hip: routing, the generic kernel, the slab reductions
 bool hdf_wgrad_apply_takes(int dtype, int stride, const WgradArgs& a);
 int hdf_launch_wgrad(int dtype, int stride, WgradArgs a, float* dw, int sc_store, int lc_store, int accumulate,
                      void* workspace, size_t workspace_bytes, hipStream_t st);
 size_t hdf_wgrad_workspace_bytes(int stride, int N, int Ds, int Hs, int Ws, int SC, int LC);
+
+// ---- conv_wgrad2.hip: the 16-bit stride-1 kernel hdf_launch_wgrad routes to.  The launcher gets the finished WgradArgs
+// (SCp, LCp, tiles, partials set) and the grid, and only picks the instantiation; the same holds for conv_wgrad_s2.hip.
+bool hdf_wgrad2_takes(int dtype, int stride, const WgradArgs& a);
+int hdf_launch_wgrad2(int dtype, const WgradArgs& a, dim3 grid, hipStream_t st);
+
+// ---- conv_wgrad_s2.hip: the 16-bit stride-2 kernel; sb = small-channel blocks per workgroup (1 or 2)
+bool hdf_wgrad_s2_takes(int dtype, int stride, const WgradArgs& a);
+int hdf_launch_wgrad_s2(int dtype, const WgradArgs& a, int sb, dim3 grid, hipStream_t st);
 
 // ---- conv_pack.hip
 // every weight pack of a training step in ONE launch (42 separate 6-us launches otherwise)

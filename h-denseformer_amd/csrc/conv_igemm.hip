@@ -7,7 +7,7 @@
 //   mode 2  ConvTranspose3d(k3,s2,p1,op1) forward, one launch z-slice per output parity class
 // This file: conv_igemm_kernel, the weights-stationary persistent conv_ws2_kernel of the high-resolution stride-1 layers, and
 // the routing of a launch (launch_conv_t).  The specialised stride-2 kernels live in conv_s2.hip, the weight gradients in
-// conv_wgrad.hip, the weight packers in conv_pack.hip, the weights-in-registers stride-1 form in conv_wr.hip.
+// conv_wgrad.hip (routing, generic kernel) with conv_wgrad2.hip / conv_wgrad_s2.hip (the 16-bit kernels), the weight packers in conv_pack.hip, the weights-in-registers stride-1 form in conv_wr.hip.
 //
 // Data layout: activations are channels-last (NDHWC) with an explicit voxel pitch, storage bf16 or
 // f32.  GEMM view: M = output voxels of a 3-D tile, N = output channels, K = taps x input channels.

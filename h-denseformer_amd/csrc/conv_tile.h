@@ -1,8 +1,9 @@
 // Pieces shared by the convolution kernels: the MFMA wrapper per storage type, the generic halo-box staging (PITCH,
 // stage_box), the MFMA-row -> tile-voxel map of the 4x8x8 tile family, the LDS-only workgroup barrier, the persistent
 // kernels' tile record, the zero line of the LDS-DMA kernels and the phase stamps of a -DWS_DBG_STAMPS build.
-// Users: conv_igemm.hip, conv_wgrad.hip and conv_s2.hip (any of it), conv_wr.hip and conv_first.hip (Mma, the row maps,
-// WS_BARRIER, WsTile).
+// Users: conv_igemm.hip, conv_s2.hip and, through conv_wgrad_tile.h, conv_wgrad.hip (stage_box, Mma, WS_BARRIER),
+// conv_wgrad2.hip (Mma, WS_BARRIER, WsTile, the stamps) and conv_wgrad_s2.hip (Mma, WS_BARRIER, the zero line); conv_wr.hip
+// and conv_first.hip (Mma, the row maps, WS_BARRIER, WsTile).
 #pragma once
 #include "hdf_common.h"
 

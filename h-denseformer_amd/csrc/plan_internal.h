@@ -155,7 +155,7 @@ struct hdf_plan {
   // ---- 2-D model (models/HDenseFormer_2D.py) run as its exact depth-replicated 3-D embedding (see embed2d.hip)
   bool is2d = false;
   // Round 6: the 2-D model runs NATIVELY on depth-1 tensors (flat): every level has depth 1, the convolutions / transposed
-  // convolutions / weight gradients are the FLAT instantiations of conv_igemm.hip / conv_s2.hip / conv_wgrad.hip (centre-plane taps of the embedded 27-tap
+  // convolutions / weight gradients are the FLAT instantiations of conv_igemm.hip / conv_s2.hip / conv_wgrad.hip (conv_wgrad_kernel; centre-plane taps of the embedded 27-tap
   // panels), pooling and up-sampling their 2-D forms (pool_ops.hip), the patch embedding contracts depth slice 0 of the
   // embedded 16^3 kernels with the input's 16 x 16 patches (K = 256).  flat = false keeps the depth-16
   // replicated embedding of rounds 3-5 (hdf_plan_create_2d_embedded: the oracle of tests/test_gpu_model_2d.py).

@@ -222,3 +222,31 @@ def test_persistent_kernel_controls_on_the_host(lib):
         assert lib.hdf_plan_chain_state(plan.h, 2, C.byref(pers), C.byref(who)) == 0 and pers.value == 0   # 256 tiles > 128
     finally:
         assert lib.hdf_set_cu_budget(256) == 0
+
+
+# (stride, N, Ds, Hs, Ws, SC, LC) -> bytes.  Recorded from the library built at the commit before conv_wgrad.hip was split
+# into three units (its size function carried the tile extents as literals of its own); the size function now reads the
+# tile table the launch reads, and must go on returning these.
+WGRAD_WORKSPACE = [
+    ((1, 2, 32, 40, 48, 32, 32), 53084160),        # stride 1, 3-D: 4x8x8 tiles
+    ((2, 2, 16, 16, 16, 64, 32), 28311552),        # stride 2, 3-D: 4x4x4 tiles
+    ((1, 2, 1, 64, 64, 32, 32), 3538944),          # stride 1, depth 1: 1x16x16 tiles
+    ((2, 2, 1, 32, 32, 32, 64), 7077888),          # stride 2, depth 1: 1x8x8 tiles
+    ((1, 1, 9, 7, 10, 32, 48), 1327104),           # ragged extents, both strides, 3-D and depth 1
+    ((2, 1, 9, 7, 10, 48, 32), 3981312),
+    ((1, 1, 1, 17, 33, 32, 32), 663552),
+    ((2, 1, 1, 9, 7, 32, 32), 221184),
+    ((1, 2, 32, 32, 32, 16, 16), 28311552),        # 16 channels: padded to 32
+    ((1, 2, 8, 8, 8, 512, 512), 100663296),        # 512 x 512 channels: the 96 MiB cap binds
+    ((2, 2, 8, 8, 8, 512, 512), 100663296),
+    ((1, 1, 8, 8, 8, 32, 32), 221184),             # fewer tiles (2, 1) than 1024 / pairs: one slab per tile
+    ((2, 1, 4, 4, 4, 32, 32), 110592),
+    ((1, 2, 128, 128, 128, 32, 64), 100663296),    # 512 slabs wanted, capped
+]
+
+
+def test_wgrad_workspace_sizes_are_pinned(lib):
+    """hdf_op_wgrad_workspace_bytes against constants recorded once from the parent commit's library: G, the number of
+    partial slabs, follows from the workspace, and G fixes the summation order of the weight gradient"""
+    for args, want in WGRAD_WORKSPACE:
+        assert lib.hdf_op_wgrad_workspace_bytes(*args) == want, args
