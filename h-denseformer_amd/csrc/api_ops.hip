@@ -204,6 +204,64 @@ int hdf_surface_asd(const uint8_t* target, const uint8_t* prediction, int label,
   return hdf_launch_surface_asd(target, prediction, label, D, H, W, workspace, (unsigned long long*)result, histogram_out,
                                 histogram_len, (hipStream_t)stream);
 }
+// the same in physical units (surface_mm.hip).  The spacing is a host pointer: checked, and read, before anything else.
+int64_t hdf_surface_mm_workspace_bytes(int D, int H, int W) {
+  if (hdf_surface_check_dims("mm_workspace_bytes", D, H, W) != HDF_OK) return -1;
+  return hdf_surface_mm_ws_bytes(D, H, W);
+}
+int hdf_op_edt_sq_mm(const uint8_t* flags, int seed_bit, int D, int H, int W, const double* spacing, double* d2,
+                     void* workspace, int64_t workspace_bytes, hdf_stream stream) {
+  SurfaceSpacing sp;
+  HDF_TRY(hdf_surface_check_spacing("edt_sq_mm", spacing, &sp));
+  HDF_TRY(hdf_surface_check_dims("edt_sq_mm", D, H, W));
+  HDF_CHECK_ARG(seed_bit >= 1 && seed_bit <= 255, "surface: edt_sq_mm: seed mask %d (1..255)", seed_bit);
+  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_mm_ws_bytes(D, H, W),
+                "surface: edt_sq_mm: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+                (long long)hdf_surface_mm_ws_bytes(D, H, W));
+  HDF_CHECK_ARG(flags && d2 && workspace, "surface: edt_sq_mm: null argument");
+  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(d2) & 7) == 0, "surface: edt_sq_mm: d2 not aligned to 8 bytes");
+  return hdf_launch_edt_sq_mm(flags, seed_bit, D, H, W, sp, d2, (hipStream_t)stream);
+}
+int hdf_op_select_u64(const uint64_t* keys, int64_t n, int64_t lo, void* workspace, int64_t workspace_bytes,
+                      uint64_t* out2, hdf_stream stream) {
+  HDF_CHECK_ARG(n >= 1 && n < ((int64_t)1 << 31), "surface: select_u64: n=%lld outside [1, 2^31)", (long long)n);
+  HDF_CHECK_ARG(lo >= 0 && lo < n, "surface: select_u64: lo=%lld outside [0, n=%lld)", (long long)lo, (long long)n);
+  HDF_CHECK_ARG(workspace_bytes >= HDF_SELECT_U64_WS, "surface: select_u64: workspace of %lld bytes, %d needed",
+                (long long)workspace_bytes, HDF_SELECT_U64_WS);
+  HDF_CHECK_ARG(keys && workspace && out2, "surface: select_u64: null argument");
+  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "surface: select_u64: workspace not aligned to 8 bytes");
+  return hdf_launch_select_u64((const unsigned long long*)keys, n, lo, workspace, (unsigned long long*)out2,
+                               (hipStream_t)stream);
+}
+int hdf_surface_distances_mm(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
+                             const double* spacing, void* workspace, int64_t workspace_bytes, uint64_t* result,
+                             hdf_stream stream) {
+  SurfaceSpacing sp;
+  HDF_TRY(hdf_surface_check_spacing("distances_mm", spacing, &sp));
+  HDF_TRY(hdf_surface_check_dims("distances_mm", D, H, W));
+  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: distances_mm: label %d (1..255)", label);
+  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_mm_ws_bytes(D, H, W),
+                "surface: distances_mm: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+                (long long)hdf_surface_mm_ws_bytes(D, H, W));
+  HDF_CHECK_ARG(target && prediction && workspace && result, "surface: distances_mm: null argument");
+  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "surface: distances_mm: workspace not aligned to 8 bytes");
+  return hdf_launch_surface_distances_mm(target, prediction, label, D, H, W, sp, workspace, (unsigned long long*)result,
+                                         (hipStream_t)stream);
+}
+int hdf_surface_asd_mm(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
+                       const double* spacing, void* workspace, int64_t workspace_bytes, uint64_t* result,
+                       hdf_stream stream) {
+  SurfaceSpacing sp;
+  HDF_TRY(hdf_surface_check_spacing("asd_mm", spacing, &sp));
+  HDF_TRY(hdf_surface_check_dims("asd_mm", D, H, W));
+  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: asd_mm: label %d (1..255)", label);
+  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_mm_ws_bytes(D, H, W), "surface: asd_mm: workspace of %lld bytes, %lld needed",
+                (long long)workspace_bytes, (long long)hdf_surface_mm_ws_bytes(D, H, W));
+  HDF_CHECK_ARG(target && prediction && workspace && result, "surface: asd_mm: null argument");
+  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "surface: asd_mm: workspace not aligned to 8 bytes");
+  return hdf_launch_surface_asd_mm(target, prediction, label, D, H, W, sp, workspace, (unsigned long long*)result,
+                                   (hipStream_t)stream);
+}
 int64_t hdf_normalize_workspace_bytes(int channels) { return (int64_t)hdf_norm_ws_bytes(channels); }
 int hdf_normalize_mr(float* image, int channels, int64_t voxels, void* workspace, hdf_stream stream) {
   HDF_CHECK_ARG(image && workspace, "normalize_mr: null argument");

@@ -1,6 +1,6 @@
 // Surface-distance evaluation (surface.hip): mask flags, the exact squared Euclidean distance transform, the gather of
 // surface distances into a histogram and the order-statistic select; the average surface distance on top of that
-// transform (surface_asd.hip).  Definitions: include/hdf.h.
+// transform (surface_asd.hip); both with a voxel spacing, in fp64 (surface_mm.hip).  Definitions: include/hdf.h.
 #pragma once
 #include "../../include/hdf.h"  // HDF_EDT_NO_SEED
 #include "hdf_common.h"
@@ -31,6 +31,10 @@ int64_t hdf_surface_hist_bins(int D, int H, int W);
 int hdf_launch_mask_flags(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, uint8_t* flags,
                           unsigned long long* counts, bool counts_are_zero, hipStream_t st);
 int hdf_launch_edt_sq(const uint8_t* flags, int seed_mask, int D, int H, int W, int32_t* d2, hipStream_t st);
+// the first pass of that transform alone (along W).  in_fp64_slots: voxel v's int32 goes to the low word of the fp64 slot
+// v (d2[2 v]) and the high words are left as they are -- where surface_mm.hip's pass along H picks it up
+int hdf_launch_edt_row(const uint8_t* flags, int seed_mask, int D, int H, int W, int32_t* d2, bool in_fp64_slots,
+                       hipStream_t st);
 int hdf_launch_surface_distances(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, void* ws,
                                  unsigned long long* result, uint32_t* hist_out, int64_t hist_len, hipStream_t st);
 
@@ -41,3 +45,20 @@ int hdf_launch_edge_flags(const uint8_t* tgt, const uint8_t* pred, int label, in
                           unsigned long long* counts, bool counts_are_zero, hipStream_t st);
 int hdf_launch_surface_asd(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, void* ws,
                            unsigned long long* result, uint32_t* hist_out, int64_t hist_len, hipStream_t st);
+
+// the same measures in physical units (surface_mm.hip): squared distances are fp64, weighted per axis by the squared spacing
+struct SurfaceSpacing {
+  double wz, wy, wx;   // fl(sz sz), fl(sy sy), fl(sx sx)
+};
+// host-side check of a spacing triple (host pointer): HDF_ERR_ARG with a "surface:" message
+int hdf_surface_check_spacing(const char* who, const double* spacing, SurfaceSpacing* out);
+int64_t hdf_surface_mm_ws_bytes(int D, int H, int W);
+int hdf_launch_edt_sq_mm(const uint8_t* flags, int seed_mask, int D, int H, int W, const SurfaceSpacing& sp, double* d2,
+                         hipStream_t st);
+// ws: HDF_SELECT_U64_WS bytes
+int hdf_launch_select_u64(const unsigned long long* keys, int64_t n, int64_t lo, void* ws, unsigned long long* out2,
+                          hipStream_t st);
+int hdf_launch_surface_distances_mm(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W,
+                                    const SurfaceSpacing& sp, void* ws, unsigned long long* result, hipStream_t st);
+int hdf_launch_surface_asd_mm(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W,
+                              const SurfaceSpacing& sp, void* ws, unsigned long long* result, hipStream_t st);

@@ -88,6 +88,8 @@ __global__ __launch_bounds__(256) void mask_flags_kernel(const uint8_t* __restri
 // count of leading / trailing zeros and the nearest one in another chunk is a wave-uniform running index.
 constexpr int ROW_CHUNKS = HDF_SURFACE_MAX_DIM / 64;
 constexpr int FAR = 1 << 20;   // "no seed on that side": any real index distance is below 2^10
+// STRIDE: int32 words from one voxel's result to the next (2: the low word of an fp64 slot, surface_mm.hip)
+template <int STRIDE>
 __global__ __launch_bounds__(256) void edt_row_kernel(const uint8_t* __restrict__ flags, int seed_mask, int64_t nlines,
                                                       int W, int32_t* __restrict__ d2) {
   const int lane = threadIdx.x & 63, nc = (W + 63) >> 6;
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(256) void edt_row_kernel(const uint8_t* __restrict_
         const int left = le ? c * 64 + 63 - __clzll((long long)le) : before[c];
         const int right = ge ? i + __ffsll((long long)ge) - 1 : after[c];
         const int d = min(i - left, right - i);
-        d2[line * W + i] = d >= FAR / 2 ? SENT : d * d;
+        d2[(line * W + i) * STRIDE] = d >= FAR / 2 ? SENT : d * d;
       }
     }
   }
@@ -342,11 +344,20 @@ int launch_col(int32_t* d2, int64_t outer, int L, int64_t inner, hipStream_t st)
 }
 }  // namespace
 
-int hdf_launch_edt_sq(const uint8_t* flags, int seed_mask, int D, int H, int W, int32_t* d2, hipStream_t st) {
+int hdf_launch_edt_row(const uint8_t* flags, int seed_mask, int D, int H, int W, int32_t* d2, bool in_fp64_slots,
+                       hipStream_t st) {
   const int64_t nlines = (int64_t)D * H;
   const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(nlines, 4), 1 << 16);
-  hipLaunchKernelGGL(edt_row_kernel, dim3(gx), dim3(256), 0, st, flags, seed_mask, nlines, W, d2);
+  if (in_fp64_slots)
+    hipLaunchKernelGGL(edt_row_kernel<2>, dim3(gx), dim3(256), 0, st, flags, seed_mask, nlines, W, d2);
+  else
+    hipLaunchKernelGGL(edt_row_kernel<1>, dim3(gx), dim3(256), 0, st, flags, seed_mask, nlines, W, d2);
   HDF_LAUNCH_CHECK();
+  return HDF_OK;
+}
+
+int hdf_launch_edt_sq(const uint8_t* flags, int seed_mask, int D, int H, int W, int32_t* d2, hipStream_t st) {
+  HDF_TRY(hdf_launch_edt_row(flags, seed_mask, D, H, W, d2, false, st));
   HDF_TRY(launch_col(d2, D, H, W, st));                  // along H: D slabs of H lines-of-W
   return launch_col(d2, 1, D, (int64_t)H * W, st);       // along D: the (h, w) plane is contiguous
 }

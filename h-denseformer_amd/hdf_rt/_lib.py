@@ -70,6 +70,11 @@ _PROTOS = {
     "hdf_surface_asd_workspace_bytes": (_i64, [_i, _i, _i]),
     "hdf_op_edge_flags": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "hdf_surface_asd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "hdf_surface_mm_workspace_bytes": (_i64, [_i, _i, _i]),
+    "hdf_op_edt_sq_mm": (_i, [_vp, _i, _i, _i, _i, _pd, _vp, _vp, _i64, _vp]),
+    "hdf_op_select_u64": (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "hdf_surface_distances_mm": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _vp, _i64, _vp, _vp]),
+    "hdf_surface_asd_mm": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _vp, _i64, _vp, _vp]),
     "hdf_normalize_workspace_bytes": (_i64, [_i]),
     "hdf_normalize_mr": (_i, [_vp, _i, _i64, _vp, _vp]),
     "hdf_normalize_petct": (_i, [_vp, _i, _i64, _f, _f, _vp, _vp]),

@@ -7,7 +7,13 @@ formed in fp64 on the host.  Definitions: include/hdf.h.  No CPU fallback.
 
 The average surface distance (reference: cal_asd, multi_asd, utils.py:165-191, MONAI's SurfaceDistanceMetric on the host)
 is a call of its own, hdf_surface_asd (csrc/surface_asd.hip): MONAI's edge set and its distance to the other EDGE SET are
-not the contour and the Maurer map of cal_score.  It leaves four integers per class; the rest is the same."""
+not the contour and the Maurer map of cal_score.  It leaves four integers per class; the rest is the same.
+
+Physical units: every wrapper takes `spacing=None`.  None is the path above, unchanged (distances in voxels).  A triple
+(sz, sy, sx) -- the voxel size along the axes of the array AS IT IS PASSED, [D, H, W] -- takes hdf_surface_distances_mm /
+hdf_surface_asd_mm (csrc/surface_mm.hip): the same flags, seed sets and contours, fp64 squared distances weighted per axis,
+an exact select over their bit patterns in place of the histogram.  The rest is the same again."""
+import ctypes
 import math
 import struct
 
@@ -25,6 +31,8 @@ _workspaces = {}
 # the same for hdf_surface_asd, which needs one histogram more: a cache of its own, so that neither call is ever handed
 # the other's allocation
 _asd_workspaces = {}
+# and for the entries that take a spacing (fp64 maps: about 17 bytes a voxel), shared by the two of them
+_mm_workspaces = {}
 ASD_KEYS = ("ASD", "ASD_pred_to_gt", "ASD_gt_to_pred")
 
 
@@ -32,6 +40,7 @@ def clear_workspaces():
     """drop the cached workspaces (a caller that is done scoring, or moves on to another volume shape)"""
     _workspaces.clear()
     _asd_workspaces.clear()
+    _mm_workspaces.clear()
 
 
 def _volume(a, what):
@@ -59,9 +68,32 @@ def _workspace(dev, shape, cache=None, size_fn="hdf_surface_workspace_bytes"):
     return ws
 
 
+def _spacing(spacing):
+    """(sz, sy, sx) as the host array of three doubles the C entries read; the entries themselves refuse a bad value"""
+    s = [float(v) for v in spacing]
+    if len(s) != 3:
+        raise ValueError(f"spacing must be (sz, sy, sx), got {spacing!r}")
+    return (ctypes.c_double * 3)(*s)
+
+
+def _f64(bits):
+    return struct.unpack("<d", struct.pack("<Q", int(bits) & 0xFFFFFFFFFFFFFFFF))[0]
+
+
+def scores_from_result_mm(row):
+    """the five numbers of cal_score in fp64 from one result[12] row of hdf_surface_distances_mm: words 5, 7 and 8 are the
+    bit patterns of squared physical distances"""
+    nT, nP, nI, _c6t, _c6p, hd2, _n, slo, shi, _lo, r, valid = (int(v) for v in row)
+    return _scores(nT, nP, nI, _f64(hd2), _f64(slo), _f64(shi), r, valid)
+
+
 def scores_from_result(row):
     """the five numbers of cal_score in fp64 from one result[12] row of hdf_surface_distances"""
     nT, nP, nI, _c6t, _c6p, hd2, _n, slo, shi, _lo, r, valid = (int(v) for v in row)
+    return _scores(nT, nP, nI, hd2, slo, shi, r, valid)
+
+
+def _scores(nT, nP, nI, hd2, slo, shi, r, valid):
     nan = float("nan")
     out = {"Jaccard": nI / (nT + nP - nI) if nT + nP - nI else nan,
            "Dice": 2 * nI / (nT + nP) if nT + nP else nan,
@@ -84,10 +116,22 @@ def _pair(target, prediction):
     return tgt, prd, tuple(int(s) for s in tgt.shape)
 
 
-def surface_scores(target, prediction, labels):
-    """one dict of KEYS per label in `labels` (each 1..255), for two uint8 volumes [D, H, W]"""
+def surface_scores(target, prediction, labels, spacing=None):
+    """one dict of KEYS per label in `labels` (each 1..255), for two uint8 volumes [D, H, W].  spacing: None (distances
+    in voxels) or the voxel size (sz, sy, sx) along the array's axes (HausdorffDistance and HausdorffDistance95 in its
+    unit, both directions)"""
     tgt, prd, shape = _pair(target, prediction)
     labels = [int(k) for k in labels]
+    if spacing is not None:
+        sp = _spacing(spacing)
+        with torch.cuda.device(tgt.device):
+            ws = _workspace(tgt.device, shape, _mm_workspaces, "hdf_surface_mm_workspace_bytes")
+            rows = torch.empty((max(len(labels), 1), 12), dtype=torch.int64, device=tgt.device)
+            for i, k in enumerate(labels):
+                check(lib().hdf_surface_distances_mm(ptr(tgt), ptr(prd), k, *shape, sp, ptr(ws), ws.numel(), ptr(rows[i]),
+                                                     stream_ptr()), "hdf_surface_distances_mm")
+            host = rows.cpu()          # the one D2H copy, after every class is enqueued
+        return [scores_from_result_mm(host[i].tolist()) for i in range(len(labels))]
     with torch.cuda.device(tgt.device):
         ws = _workspace(tgt.device, shape)
         rows = torch.empty((max(len(labels), 1), 12), dtype=torch.int64, device=tgt.device)
@@ -98,33 +142,37 @@ def surface_scores(target, prediction, labels):
     return [scores_from_result(host[i].tolist()) for i in range(len(labels))]
 
 
-def cal_score(predict, target):
+def cal_score(predict, target, spacing=None):
     """metrics.cal_score(predict, target) for two boolean or uint8 masks (non-zero = inside): a dict of KEYS.  The
-    reference's FalseNegativeError / FalsePositiveError are left out (none of its wrappers reads them)."""
+    reference's FalseNegativeError / FalsePositiveError are left out (none of its wrappers reads them).  spacing: as
+    surface_scores -- what the reference gets from the SimpleITK images it is handed (useImageSpacing=True)."""
     prd, tgt = _volume(predict, "predict"), _volume(target, "target")
-    return surface_scores((tgt != 0).to(torch.uint8), (prd != 0).to(torch.uint8), [1])[0]
+    return surface_scores((tgt != 0).to(torch.uint8), (prd != 0).to(torch.uint8), [1], spacing)[0]
 
 
-def _multi(key, y_true, y_pred, num_classes):
-    vals = [round(s[key], 4) for s in surface_scores(y_true, y_pred, range(1, num_classes + 1))]
+def _multi(key, y_true, y_pred, num_classes, spacing=None):
+    vals = [round(s[key], 4) for s in surface_scores(y_true, y_pred, range(1, num_classes + 1), spacing)]
     return vals, round(np.mean(vals), 4)
 
 
-def multi_dice(y_true, y_pred, num_classes):
-    return _multi("Dice", y_true, y_pred, num_classes)
+def multi_dice(y_true, y_pred, num_classes, spacing=None):
+    """(spacing does not enter an overlap measure; it selects the call that computes them all)"""
+    return _multi("Dice", y_true, y_pred, num_classes, spacing)
 
 
-def multi_hd(y_true, y_pred, num_classes):
-    """per-class HausdorffDistance95, like the reference's multi_hd"""
-    return _multi("HausdorffDistance95", y_true, y_pred, num_classes)
+def multi_hd(y_true, y_pred, num_classes, spacing=None):
+    """per-class HausdorffDistance95, like the reference's multi_hd; in the unit of `spacing` = (sz, sy, sx) when given"""
+    return _multi("HausdorffDistance95", y_true, y_pred, num_classes, spacing)
 
 
-def multi_vs(y_true, y_pred, num_classes):
-    return _multi("VolumeSimilarity", y_true, y_pred, num_classes)
+def multi_vs(y_true, y_pred, num_classes, spacing=None):
+    """(spacing: as multi_dice)"""
+    return _multi("VolumeSimilarity", y_true, y_pred, num_classes, spacing)
 
 
-def multi_jc(y_true, y_pred, num_classes):
-    return _multi("Jaccard", y_true, y_pred, num_classes)
+def multi_jc(y_true, y_pred, num_classes, spacing=None):
+    """(spacing: as multi_dice)"""
+    return _multi("Jaccard", y_true, y_pred, num_classes, spacing)
 
 
 # ------------------------------------------------------------------------------------------- average surface distance
@@ -146,10 +194,21 @@ def asd_from_result(row):
     return {"ASD": sym, "ASD_pred_to_gt": directed(sum_a, n_p, n_t), "ASD_gt_to_pred": directed(sum_b, n_t, n_p)}
 
 
-def asd_scores(target, prediction, labels):
-    """one dict of ASD_KEYS per label in `labels` (each 1..255), for two uint8 volumes [D, H, W]"""
+def asd_scores(target, prediction, labels, spacing=None):
+    """one dict of ASD_KEYS per label in `labels` (each 1..255), for two uint8 volumes [D, H, W].  spacing: None
+    (distances in voxels) or the voxel size (sz, sy, sx) along the axes of the arrays as they are passed"""
     tgt, prd, shape = _pair(target, prediction)
     labels = [int(k) for k in labels]
+    if spacing is not None:
+        sp = _spacing(spacing)
+        with torch.cuda.device(tgt.device):
+            ws = _workspace(tgt.device, shape, _mm_workspaces, "hdf_surface_mm_workspace_bytes")
+            rows = torch.empty((max(len(labels), 1), 4), dtype=torch.int64, device=tgt.device)
+            for i, k in enumerate(labels):
+                check(lib().hdf_surface_asd_mm(ptr(tgt), ptr(prd), k, *shape, sp, ptr(ws), ws.numel(), ptr(rows[i]),
+                                               stream_ptr()), "hdf_surface_asd_mm")
+            host = rows.cpu()          # the one D2H copy, after every class is enqueued
+        return [asd_from_result(host[i].tolist()) for i in range(len(labels))]
     with torch.cuda.device(tgt.device):
         ws = _workspace(tgt.device, shape, _asd_workspaces, "hdf_surface_asd_workspace_bytes")
         rows = torch.empty((max(len(labels), 1), 4), dtype=torch.int64, device=tgt.device)
@@ -169,16 +228,20 @@ def _mask(a, what):
     return (_volume(a, what) != 0).to(torch.uint8)
 
 
-def cal_asd(predict, target):
+def cal_asd(predict, target, spacing=None):
     """utils.cal_asd(predict, target) for one pair of boolean or uint8 masks (non-zero = inside), [D, H, W] or the
-    reference's [1, 1, a, b, c], numpy or torch, host or device: MONAI's symmetric average surface distance as a float"""
+    reference's [1, 1, a, b, c], numpy or torch, host or device: MONAI's symmetric average surface distance as a float.
+    spacing: None, or (sz, sy, sx) along the three volume axes of the masks as they are passed (what MONAI hands to
+    scipy's distance_transform_edt(sampling=...))"""
     prd, tgt = _mask(predict, "predict"), _mask(target, "target")
-    return asd_scores(tgt, prd, [1])[0]["ASD"]
+    return asd_scores(tgt, prd, [1], spacing)[0]["ASD"]
 
 
-def multi_asd(y_true, y_pred, num_classes):
+def multi_asd(y_true, y_pred, num_classes, spacing=None):
     """utils.multi_asd(y_true, y_pred, num_classes) for two label maps [D, H, W]: (per-class ASD rounded to 4 places,
     their mean rounded likewise); an inf or a NaN goes through np.mean as it does in the reference.  The reference's
-    permute(1, 2, 0) only renames the axes (unit spacing): the maps are taken as they are."""
-    vals = [round(s["ASD"], 4) for s in asd_scores(y_true, y_pred, range(1, num_classes + 1))]
+    permute(1, 2, 0) only renames the axes (unit spacing): the maps are taken as they are.  With a spacing that renaming
+    matters: the reference permutes the axes BEFORE MONAI sees them, so a spacing given there is in the permuted order.
+    Here `spacing` = (sz, sy, sx) follows the axes of the arrays the caller passes, [D, H, W], and nothing is permuted."""
+    vals = [round(s["ASD"], 4) for s in asd_scores(y_true, y_pred, range(1, num_classes + 1), spacing)]
     return vals, round(np.mean(vals), 4)

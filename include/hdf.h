@@ -336,6 +336,45 @@ int hdf_surface_asd(const uint8_t* target, const uint8_t* prediction, int label,
                     void* workspace, int64_t workspace_bytes, uint64_t* result, uint32_t* histogram_out,
                     int64_t histogram_len, hdf_stream stream);
 
+/* ---- the same measures in physical units: a voxel spacing for HD, HD95 and ASD.  spacing = (sz, sy, sx), a HOST pointer
+ * to three doubles in the axis order of the [D][H][W] array; the weights are wz = fl(sz sz), wy = fl(sy sy), wx = fl(sx sx)
+ * in fp64.  For a seed set M,
+ *   D2_M(v) = min over the seeds u in M of fl( fl(wz a^2) + fl( fl(wy b^2) + fl(wx c^2) ) ),  (a, b, c) = |v - u| per axis,
+ * where a^2, b^2, c^2 are exact integers and every fl is one IEEE fp64 rounding (no fused multiply-add); +inf where M is
+ * empty.  The separable transform (c^2 along W as an integer, then H, then D) computes exactly this minimum, because
+ * fl(x + y) and fl(w k) are monotone; with spacing (1, 1, 1) every value equals the integer of hdf_op_edt_sq.
+ * Flags, seed sets and contour / edge sets are those of the unit-spacing entries (hdf_op_mask_flags: seeds B26, contour
+ * C6; hdf_op_edge_flags: E6); only the metric changes.
+ * hdf_op_edt_sq_mm: d2[v] fp64 = D2_M(v) for M = the voxels with (flags[v] & seed_bit).
+ * hdf_op_select_u64: out2[0] = sorted[lo], out2[1] = sorted[min(lo + 1, n - 1)] of n uint64 keys (device), an exact
+ * multi-pass radix select: integer atomics only, no sort, no host round trip, the same bits from run to run.  Its
+ * workspace is HDF_SELECT_U64_WS bytes (never above hdf_surface_mm_workspace_bytes).  Non-negative doubles order like
+ * their bit patterns: hdf_surface_distances_mm runs this select over the bit patterns of the surface distances.
+ * hdf_surface_distances_mm: result[12] uint64 laid out like hdf_surface_distances with d2_T = D2_B26(T), d2_P = D2_B26(P):
+ * words 5, 7 and 8 (hd2, S[lo], S[hi]) are the fp64 BIT PATTERNS of squared physical distances, S is sorted as fp64, the
+ * other words are the same integers; `valid` as there, and words 5..10 are 0 when it is 0.
+ * hdf_surface_asd_mm: result[4] uint64 = |E6(T)| |E6(P)| bits(sum A) bits(sum B) with A = { sqrt(D2_E6(T)(v)) : v in E6(P) },
+ * B = { sqrt(D2_E6(P)(v)) : v in E6(T) }: fp64 sums over contiguous runs of voxels whose bounds follow from D*H*W alone,
+ * then one fixed tree -- no floating-point atomics, two calls agree in every bit.  Both sums are +0 when either edge set
+ * is empty.
+ * Refused (HDF_ERR_ARG, "surface: ...") before anything is launched, the spacing first: a null spacing; a component that
+ * is not finite, not positive or outside [2^-10, 2^10]; whatever the unit-spacing entries refuse; a workspace below
+ * hdf_surface_mm_workspace_bytes(D, H, W) (one size for the three entries that take a volume, about 17 bytes a voxel;
+ * -1 for refused dimensions); hdf_op_select_u64: n < 1, n >= 2^31, lo outside 0..n-1, a workspace below
+ * HDF_SELECT_U64_WS.  Pointers other than spacing are device memory; stream ordering and workspace reuse as above. */
+#define HDF_SELECT_U64_WS 49408 /* six histograms of 2048 uint32, then the state */
+int64_t hdf_surface_mm_workspace_bytes(int D, int H, int W);
+int hdf_op_edt_sq_mm(const uint8_t* flags, int seed_bit, int D, int H, int W, const double* spacing, double* d2,
+                     void* workspace, int64_t workspace_bytes, hdf_stream stream);
+int hdf_op_select_u64(const uint64_t* keys, int64_t n, int64_t lo, void* workspace, int64_t workspace_bytes,
+                      uint64_t* out2, hdf_stream stream);
+int hdf_surface_distances_mm(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
+                             const double* spacing, void* workspace, int64_t workspace_bytes, uint64_t* result,
+                             hdf_stream stream);
+int hdf_surface_asd_mm(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
+                       const double* spacing, void* workspace, int64_t workspace_bytes, uint64_t* result,
+                       hdf_stream stream);
+
 /* ---- input normalisation on the device, in place on one fp32 sample [channels][voxels] -----------------------
  * hdf_normalize_mr: MRNormalize (data_utils/data_loader.py:39-50): every channel divided by its maximum when that is
  * non-zero, then negatives clamped to 0.  hdf_normalize_petct: PETandCTNormalize (:53-68): channel 0 ->
