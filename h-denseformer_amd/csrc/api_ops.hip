@@ -1,5 +1,5 @@
 // Process state (last error, compute-unit budget) and the one-to-one C ABI wrappers of the operator launchers: losses,
-// metrics, surface distances, normalisation, sliding window, augmentation, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
+// metrics, surface distances, connected components, normalisation, sliding window, augmentation, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
 #include <atomic>
 #include <algorithm>
 #include <cstdarg>
@@ -7,6 +7,7 @@
 
 #include "../../include/hdf.h"
 #include "augment.h"
+#include "components.h"
 #include "conv_igemm.h"
 #include "loss.h"
 #include "metrics.h"
@@ -261,6 +262,52 @@ int hdf_surface_asd_mm(const uint8_t* target, const uint8_t* prediction, int lab
   HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "surface: asd_mm: workspace not aligned to 8 bytes");
   return hdf_launch_surface_asd_mm(target, prediction, label, D, H, W, sp, workspace, (unsigned long long*)result,
                                    (hipStream_t)stream);
+}
+// connected components (components.hip)
+int64_t hdf_cc_workspace_bytes(int D, int H, int W) {
+  if (hdf_cc_check_dims("workspace_bytes", D, H, W) != HDF_OK) return -1;
+  return hdf_cc_ws_bytes(D, H, W);
+}
+int hdf_cc_label(const uint8_t* volume, int label, int connectivity, int D, int H, int W, int32_t* ids, uint64_t* result,
+                 void* workspace, int64_t workspace_bytes, hdf_stream stream) {
+  HDF_TRY(hdf_cc_check_dims("label", D, H, W));
+  HDF_CHECK_ARG(connectivity == 6 || connectivity == 18 || connectivity == 26, "components: label: connectivity %d (6, 18 or 26)",
+                connectivity);
+  HDF_CHECK_ARG(label >= 0 && label <= 255, "components: label: label %d (0..255)", label);
+  HDF_CHECK_ARG(volume && ids && result && workspace, "components: label: null argument");
+  HDF_CHECK_ARG(workspace_bytes >= hdf_cc_ws_bytes(D, H, W), "components: label: workspace of %lld bytes, %lld needed",
+                (long long)workspace_bytes, (long long)hdf_cc_ws_bytes(D, H, W));
+  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "components: label: workspace not aligned to 8 bytes");
+  const int64_t V = (int64_t)D * H * W;
+  HDF_CHECK_ARG(!hdf_cc_overlap(volume, V, ids, V * 4), "components: label: ids overlaps volume");
+  return hdf_launch_cc_label(volume, label, connectivity, D, H, W, ids, (unsigned long long*)result, workspace,
+                             (hipStream_t)stream);
+}
+int hdf_cc_table(const uint8_t* volume, const int32_t* ids, const float* score, int D, int H, int W, int64_t capacity,
+                 int64_t* table, float* score_max, hdf_stream stream) {
+  HDF_TRY(hdf_cc_check_dims("table", D, H, W));
+  HDF_CHECK_ARG(capacity >= 1 && capacity < ((int64_t)1 << 31), "components: table: capacity %lld (1..2^31-1)",
+                (long long)capacity);
+  HDF_CHECK_ARG(volume && ids && table && (!score || score_max), "components: table: null argument");
+  const int64_t V = (int64_t)D * H * W;
+  HDF_CHECK_ARG(!hdf_cc_overlap(volume, V, ids, V * 4), "components: table: ids overlaps volume");
+  return hdf_launch_cc_table(volume, ids, score, D, H, W, capacity, (long long*)table, score_max, (hipStream_t)stream);
+}
+int hdf_cc_filter(const uint8_t* volume, const int32_t* ids, int D, int H, int W, int64_t min_size, int keep_largest,
+                  uint8_t* out, uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream) {
+  HDF_TRY(hdf_cc_check_dims("filter", D, H, W));
+  HDF_CHECK_ARG(min_size >= 0, "components: filter: min_size %lld is negative", (long long)min_size);
+  HDF_CHECK_ARG(volume && ids && out && result && workspace, "components: filter: null argument");
+  HDF_CHECK_ARG(workspace_bytes >= hdf_cc_ws_bytes(D, H, W), "components: filter: workspace of %lld bytes, %lld needed",
+                (long long)workspace_bytes, (long long)hdf_cc_ws_bytes(D, H, W));
+  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "components: filter: workspace not aligned to 8 bytes");
+  const int64_t V = (int64_t)D * H * W;
+  HDF_CHECK_ARG(!hdf_cc_overlap(volume, V, ids, V * 4) && !hdf_cc_overlap(out, V, ids, V * 4),
+                "components: filter: ids overlaps volume or out");
+  HDF_CHECK_ARG(out == volume || !hdf_cc_overlap(out, V, volume, V),
+                "components: filter: out overlaps volume without being volume");
+  return hdf_launch_cc_filter(volume, ids, D, H, W, min_size, keep_largest, out, (unsigned long long*)result, workspace,
+                              (hipStream_t)stream);
 }
 int64_t hdf_normalize_workspace_bytes(int channels) { return (int64_t)hdf_norm_ws_bytes(channels); }
 int hdf_normalize_mr(float* image, int channels, int64_t voxels, void* workspace, hdf_stream stream) {

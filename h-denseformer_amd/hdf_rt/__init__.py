@@ -6,6 +6,8 @@ _AUGMENT = ("TrainTransform2D", "TrainTransform3D", "augment_2d", "augment_3d", 
             "noise2d_flag", "zoom2d_canvas", "zoom_2d", "crop_resize", "resize_3d", "trunc_normalize_")
 _SURFACE = ("cal_score", "multi_dice", "multi_hd", "multi_jc", "multi_vs", "surface_scores",
             "asd_from_result", "asd_scores", "cal_asd", "multi_asd")
+_COMPONENTS = ("connected_components", "component_table", "component_stats", "keep_largest_component",
+               "remove_small_components")
 
 
 def __getattr__(name):
@@ -16,8 +18,11 @@ def __getattr__(name):
     if name in _SURFACE:
         from . import surface
         return getattr(surface, name)
+    if name in _COMPONENTS:
+        from . import components
+        return getattr(components, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def __dir__():
-    return sorted(list(globals()) + list(_AUGMENT) + list(_SURFACE))
+    return sorted(list(globals()) + list(_AUGMENT) + list(_SURFACE) + list(_COMPONENTS))

@@ -75,6 +75,10 @@ _PROTOS = {
     "hdf_op_select_u64": (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "hdf_surface_distances_mm": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _vp, _i64, _vp, _vp]),
     "hdf_surface_asd_mm": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _vp, _i64, _vp, _vp]),
+    "hdf_cc_workspace_bytes": (_i64, [_i, _i, _i]),
+    "hdf_cc_label": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "hdf_cc_table": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp]),
+    "hdf_cc_filter": (_i, [_vp, _vp, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _i64, _vp]),
     "hdf_normalize_workspace_bytes": (_i64, [_i]),
     "hdf_normalize_mr": (_i, [_vp, _i, _i64, _vp, _vp]),
     "hdf_normalize_petct": (_i, [_vp, _i, _i64, _f, _f, _vp, _vp]),

@@ -41,6 +41,8 @@ def clear_workspaces():
     _workspaces.clear()
     _asd_workspaces.clear()
     _mm_workspaces.clear()
+    from . import components
+    components.clear_workspaces()      # the connected-component entries keep a cache of their own
 
 
 def _volume(a, what):

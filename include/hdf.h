@@ -375,6 +375,44 @@ int hdf_surface_asd_mm(const uint8_t* target, const uint8_t* prediction, int lab
                        const double* spacing, void* workspace, int64_t workspace_bytes, uint64_t* result,
                        hdf_stream stream);
 
+/* ---- connected components of a label map (the reference has no such code: its users run scipy.ndimage.label and
+ * find_objects on the host).  volume: uint8 [D][H][W] on the device.
+ *   connectivity 6 / 18 / 26 = scipy's generate_binary_structure(3, 1 / 2 / 3): neighbours that differ by +-1 in at most
+ *            1 / 2 / 3 coordinates.  A neighbour outside the volume does not exist.  A depth-1 volume is the 2-D case:
+ *            6 / 18 / 26 are then the 4- / 8- / 8-neighbourhood by themselves.
+ *   adjacent = neighbours under `connectivity` that hold the SAME non-zero value: two classes that touch never merge.
+ *   label    = 0: every non-zero voxel is foreground, each value forming its own components; k in 1..255: only the voxels
+ *            equal to k are.
+ *   ids      = the components numbered 1..n in ascending order of their smallest linear voxel index, 0 for background.
+ *            For one value this is scipy.ndimage.label's numbering; for several, the per-value labels renumbered by
+ *            first voxel.  The result is unique: two calls agree in every element.
+ * hdf_cc_label: ids[v] int32 for every voxel, result[2] uint64 = n, the number of foreground voxels.
+ * hdf_cc_table: table[capacity][9] int64, row id-1 = size, value, first linear voxel index, zmin, zmax, ymin, ymax, xmin,
+ * xmax (maxima inclusive) of component id, for the ids of hdf_cc_label on the same volume.  Components with id > capacity
+ * are left out; rows n .. capacity-1 are all zeros.  score (nullable): a fp32 volume of non-negative values (a class
+ * probability); score_max[id-1] (required with score, untouched without) = its maximum over the component, exact, 0 in
+ * the rows past n.  The maximum is taken over the bit patterns read as signed integers: a negative score (-0 included)
+ * counts as +0, and a NaN with a clear sign bit wins over every number -- either is the caller's error.
+ * hdf_cc_filter: out[v] = volume[v] where the component of v is kept, 0 elsewhere (background and the voxels with
+ * ids[v] = 0 included).  A component is kept iff size >= min_size and, when keep_largest != 0, it is the largest
+ * component of its value, a tie going to the smallest id (np.argmax of the size list).  result[2] uint64 = components
+ * kept, voxels kept.  out may be volume (in place), and may not overlap it otherwise.
+ * Only integer atomics (add / min / max / compare-and-swap) are used, so no output depends on arrival order.  No kernel
+ * waits on another workgroup and every loop is bounded by the volume (csrc/components.hip).  All pointers are device
+ * memory, the kernels are ordered on `stream`, nothing waits on the host, and a workspace may be reused by the next call
+ * on the same stream without clearing.  Refused (HDF_ERR_ARG, message "components: ...") before anything is launched: a
+ * dimension outside 1..1024, D*H*W >= 2^31, connectivity not 6 / 18 / 26, label outside 0..255, capacity < 1 (or >= 2^31),
+ * min_size < 0, a null required pointer, a workspace below hdf_cc_workspace_bytes(D, H, W) (one size for hdf_cc_label and
+ * hdf_cc_filter, about 5 bytes a voxel; -1 for refused dimensions) or not aligned to 8 bytes, ids overlapping volume (or
+ * out). */
+int64_t hdf_cc_workspace_bytes(int D, int H, int W);
+int hdf_cc_label(const uint8_t* volume, int label, int connectivity, int D, int H, int W, int32_t* ids, uint64_t* result,
+                 void* workspace, int64_t workspace_bytes, hdf_stream stream);
+int hdf_cc_table(const uint8_t* volume, const int32_t* ids, const float* score, int D, int H, int W, int64_t capacity,
+                 int64_t* table, float* score_max, hdf_stream stream);
+int hdf_cc_filter(const uint8_t* volume, const int32_t* ids, int D, int H, int W, int64_t min_size, int keep_largest,
+                  uint8_t* out, uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream);
+
 /* ---- input normalisation on the device, in place on one fp32 sample [channels][voxels] -----------------------
  * hdf_normalize_mr: MRNormalize (data_utils/data_loader.py:39-50): every channel divided by its maximum when that is
  * non-zero, then negatives clamped to 0.  hdf_normalize_petct: PETandCTNormalize (:53-68): channel 0 ->

@@ -6,6 +6,7 @@ bounded host-side restatement of what the reference does for the same call (nump
   python tools/bench_rows.py augment2d                          (the 2-D training chain row alone)
   python tools/bench_rows.py transforms2d                       (the full 2-D transform list row alone)
   python tools/bench_rows.py resize3d                           (the CropResize row alone)
+  python tools/bench_rows.py components                         (the connected-component rows alone)
 """
 import json
 import os
@@ -225,6 +226,62 @@ def resize3d_row(C=2, n_cls=3, src=(173, 191, 205), S=144):
          achieved_GBps=by / us / 1e3, hbm_peak_GBps=8000, cpu_baseline=cpu)
 
 
+def components_row(shapes=((144, 144, 144), (448, 512, 512)), connectivity=26):
+    """hdf_cc_label, hdf_cc_filter (keep the largest component of each value) and hdf_cc_table (4096 rows, no score), each
+    timed alone on a three-class blob map -- a smoothed 1/8-resolution noise field, thresholded and repeated 8x along each
+    axis -- next to scipy.ndimage.label + find_objects per class on the same array, one host thread, copies not counted"""
+    from hdf_rt._lib import check, lib, ptr, stream_ptr
+    for shape in shapes:
+        rng = np.random.default_rng(15)
+        try:
+            from scipy import ndimage as ndi
+            low = ndi.gaussian_filter(rng.random(tuple(s // 8 for s in shape)), 1.5, mode="nearest")
+        except ImportError:
+            ndi, low = None, rng.random(tuple(s // 8 for s in shape))
+        cls = np.digitize(low, np.quantile(low, [0.6, 0.8, 0.93])).astype(np.uint8)
+        vol_np = np.ascontiguousarray(cls.repeat(8, 0).repeat(8, 1).repeat(8, 2))
+        vol = torch.from_numpy(vol_np).to(DEV)
+        V = vol.numel()
+        ws = torch.empty(lib().hdf_cc_workspace_bytes(*shape), dtype=torch.uint8, device=DEV)
+        ids = torch.empty(shape, dtype=torch.int32, device=DEV)
+        out = torch.empty_like(vol)
+        res = torch.empty(2, dtype=torch.int64, device=DEV)
+        table = torch.empty((4096, 9), dtype=torch.int64, device=DEV)
+        st = stream_ptr()
+
+        def label():
+            check(lib().hdf_cc_label(ptr(vol), 0, connectivity, *shape, ptr(ids), ptr(res), ptr(ws), ws.numel(), st), "label")
+
+        us_label = 1e3 * gpu_ms(label, reps=30, warm=5)
+        n, fg = res.cpu().tolist()
+        us_filter = 1e3 * gpu_ms(lambda: check(lib().hdf_cc_filter(ptr(vol), ptr(ids), *shape, 0, 1, ptr(out), ptr(res), ptr(ws),
+                                                                    ws.numel(), st), "filter"), reps=30, warm=5)
+        kept = res.cpu().tolist()
+        us_table = 1e3 * gpu_ms(lambda: check(lib().hdf_cc_table(ptr(vol), ptr(ids), None, *shape, 4096, ptr(table), None, st),
+                                              "table"), reps=30, warm=5)
+        if ndi is not None:
+            import scipy
+            struct = ndi.generate_binary_structure(3, 3)
+
+            def ref_chain():
+                for k in (1, 2, 3):
+                    lab, _ = ndi.label(vol_np == k, struct)
+                    ndi.find_objects(lab)
+
+            cpu = {"kind": "port", "what": f"scipy {scipy.__version__} ndimage.label + find_objects, three classes, structure 3x3x3",
+                   "s_per_volume": cpu_s(ref_chain, reps=1), "threads": 1}
+        else:
+            cpu = {"kind": "not measured", "what": "scipy is not installed"}
+        emit(row="connected components", config=f"{shape[0]}x{shape[1]}x{shape[2]} uint8, three classes, connectivity {connectivity}, label 0",
+             components=n, foreground_voxels=fg, kept=kept, hdf_cc_label_us=us_label, hdf_cc_filter_us=us_filter,
+             hdf_cc_table_us=us_table, voxels=V, label_ns_per_voxel=us_label * 1e3 / V, cpu_baseline=cpu)
+        del vol, ws, ids, out
+        torch.cuda.empty_cache()
+
+
+if sys.argv[1:] == ["components"]:
+    components_row()
+    sys.exit(0)
 if sys.argv[1:] == ["resize3d"]:
     resize3d_row()
     sys.exit(0)
