@@ -330,6 +330,23 @@ int hdf_sw_finalize(const float* prob_sum, const float* count, int n_cls, int64_
   HDF_CHECK_ARG(prob_sum && count && label, "sw_finalize: null argument");
   return hdf_launch_sw_finalize(prob_sum, count, n_cls, voxels, label, (hipStream_t)stream);
 }
+int hdf_sw_gather(const float* image, int channels, int D, int H, int W, int z0, int y0, int x0, int ed, int eh, int ew,
+                  int Pd, int Ph, int Pw, unsigned mirror_mask, float* out, hdf_stream stream) {
+  HDF_CHECK_ARG(image && out, "sw_gather: null argument");
+  return hdf_launch_sw_gather(image, channels, D, H, W, z0, y0, x0, ed, eh, ew, Pd, Ph, Pw, mirror_mask, out,
+                              (hipStream_t)stream);
+}
+int hdf_sw_importance_floor(const double* tables, int ed, int eh, int ew, float* floor_out, hdf_stream stream) {
+  HDF_CHECK_ARG(tables && floor_out, "sw_importance_floor: null argument");
+  return hdf_launch_sw_importance_floor(tables, ed, eh, ew, floor_out, (hipStream_t)stream);
+}
+int hdf_sw_accumulate_tta(int dtype, const void* logits, unsigned mirror_mask, int n_cls, int ed, int eh, int ew, int Pd,
+                          int Ph, int Pw, const double* tables, const float* floor, float* prob_sum, float* weight_sum,
+                          int D, int H, int W, int z0, int y0, int x0, hdf_stream stream) {
+  HDF_CHECK_ARG(logits && prob_sum && weight_sum, "sw_accumulate_tta: null argument");
+  return hdf_launch_sw_accumulate_tta(dtype, logits, mirror_mask, n_cls, ed, eh, ew, Pd, Ph, Pw, tables, floor, prob_sum,
+                                      weight_sum, D, H, W, z0, y0, x0, (hipStream_t)stream);
+}
 int hdf_onehot_from_labels(const uint8_t* labels, float* onehot, int batch, int n_cls, int64_t voxels,
                            hdf_stream stream) {
   HDF_CHECK_ARG(labels && onehot, "onehot_from_labels: null argument");

@@ -1,4 +1,4 @@
-// The evaluation path (metrics.hip): the on-device Dice metric and the sliding-window inference tail.
+// The evaluation path (metrics.hip, sw_infer.hip): the on-device Dice metric and the sliding-window inference tail.
 #pragma once
 #include "loss.h"  // HDF_CLASS_SLOTS
 
@@ -14,3 +14,11 @@ int hdf_launch_confusion_labels(const uint8_t* tgt, const uint8_t* pred, int C, 
 int hdf_launch_sw_accumulate(int dtype, const void* logits, int C, int pd, int ph, int pw, float* psum, float* cnt,
                              int D, int H, int W, int z0, int y0, int x0, hipStream_t st);
 int hdf_launch_sw_finalize(const float* psum, const float* cnt, int C, int64_t V, uint8_t* label, hipStream_t st);
+// sw_infer.hip: the window's K mirrored copies for the forward, the floor of its importance map, and the tail that
+// un-mirrors, averages and accumulates the K softmaxes under that map
+int hdf_launch_sw_gather(const float* image, int C, int D, int H, int W, int z0, int y0, int x0, int ed, int eh, int ew,
+                         int Pd, int Ph, int Pw, unsigned mask, float* out, hipStream_t st);
+int hdf_launch_sw_importance_floor(const double* tables, int ed, int eh, int ew, float* floor_out, hipStream_t st);
+int hdf_launch_sw_accumulate_tta(int dtype, const void* logits, unsigned mask, int C, int ed, int eh, int ew, int Pd, int Ph,
+                                 int Pw, const double* tables, const float* floor, float* psum, float* wsum, int D, int H,
+                                 int W, int z0, int y0, int x0, hipStream_t st);

@@ -8,9 +8,13 @@ _SURFACE = ("cal_score", "multi_dice", "multi_hd", "multi_jc", "multi_vs", "surf
             "asd_from_result", "asd_scores", "cal_asd", "multi_asd")
 _COMPONENTS = ("connected_components", "component_table", "component_stats", "keep_largest_component",
                "remove_small_components")
+_INFERENCE = ("cal_steps", "gaussian_tables", "sliding_window_predict")
 
 
 def __getattr__(name):
+    if name in _INFERENCE:
+        from . import inference
+        return getattr(inference, name)
     # `from hdf_rt import augment_3d` works, but `import hdf_rt` alone still loads neither torch nor numpy
     if name in _AUGMENT:
         from . import augment
@@ -25,4 +29,4 @@ def __getattr__(name):
 
 
 def __dir__():
-    return sorted(list(globals()) + list(_AUGMENT) + list(_SURFACE) + list(_COMPONENTS))
+    return sorted(list(globals()) + list(_AUGMENT) + list(_SURFACE) + list(_COMPONENTS) + list(_INFERENCE))

@@ -2,7 +2,9 @@
 trainer.py:488-618).  The reference runs every window through the net, takes the softmax on the GPU, then adds into two
 full-size fp32 accumulators with indexed torch ops and finally argmaxes a softmax of their quotient on the GPU and
 moves it to the host.  Here the per-window tail (softmax + accumulate + count) is ONE HIP kernel reading the logits
-once, the vote is one kernel writing a uint8 map; the model is the MI355X-native HDenseFormer.  No CPU fallback."""
+once, the vote is one kernel writing a uint8 map; the model is the MI355X-native HDenseFormer.  No CPU fallback.
+Two options the reference only sketches stay on the device as well: its Gaussian importance map (get_gaussian,
+trainer.py:620-638, bit for bit) and mirror test-time augmentation (csrc/sw_infer.hip)."""
 import numpy as np
 import torch
 
@@ -27,16 +29,106 @@ def cal_steps(image_size, patch_size, step_size):
     return origins
 
 
+def gaussian_tables(extent, sigma_scale=1. / 8):
+    """Per-axis factors of the reference's importance map (SemanticSeg.get_gaussian, trainer.py:620-638): three fp64
+    vectors tz, ty, tx such that scipy.ndimage.gaussian_filter of a unit impulse at the centre n // 2 of every axis,
+    sigma = n * sigma_scale, mode='constant', equals (tz[z] * ty[y]) * tx[x] in every bit.  Per axis that filter is a
+    correlation with the kernel exp(-0.5 / sigma^2 * j^2), |j| <= int(4 sigma + 0.5), normalised to sum 1: of the impulse
+    it leaves the kernel itself, cut where it leaves the axis.  Host-side numpy; include/hdf.h (hdf_sw_accumulate_tta)
+    states how the kernels turn the tables into weights."""
+    tables = []
+    for n in extent:
+        n = int(n)
+        sigma = n * float(sigma_scale)
+        if n < 1 or not sigma > 0:
+            raise ValueError(f"gaussian_tables: extent {tuple(extent)} and sigma_scale {sigma_scale} must be positive")
+        r = int(4.0 * sigma + 0.5)
+        k = np.exp(-0.5 / (sigma * sigma) * np.arange(-r, r + 1) ** 2)
+        k = k / k.sum()
+        off = np.arange(n) - n // 2
+        inside = np.abs(off) <= r
+        t = np.zeros(n, dtype=np.float64)
+        t[inside] = k[off[inside] + r]
+        tables.append(t)
+    return tuple(tables)
+
+
+def _mirror_mask(mirror_axes):
+    """axes of [D, H, W] -> the C ABI's mask (bit 0 = z, 1 = y, 2 = x)"""
+    mask = 0
+    for a in tuple(mirror_axes):
+        if isinstance(a, bool) or not isinstance(a, (int, np.integer)) or a not in (0, 1, 2) or mask >> int(a) & 1:
+            raise ValueError(f"mirror_axes must be a subset of (0, 1, 2) without repeats, got {mirror_axes!r}")
+        mask |= 1 << int(a)
+    return mask
+
+
+def _accumulate_tta(net, image, origins, ext, patch, psum, wsum, window_batch, mask, tables):
+    """The window loop with importance weights (tables: gaussian_tables of the extent, or None) and / or mirroring: per
+    group of windows one hdf_sw_gather per window into the forward's batch [windows x K variants], one forward, one
+    hdf_sw_accumulate_tta per window.  The tables and the map's floor go to the device once; nothing waits on the host."""
+    dev = image.device
+    n_cls, size, ch = psum.shape[0], tuple(psum.shape[1:]), image.shape[0]
+    K = 1 << bin(mask).count("1")
+    tab = floor = None
+    if tables is not None:
+        tab = torch.from_numpy(np.concatenate(tables)).to(dev)
+        floor = torch.empty(1, device=dev)
+        check(lib().hdf_sw_importance_floor(ptr(tab), *ext, ptr(floor), stream_ptr()), "hdf_sw_importance_floor")
+    per_group = max(1, window_batch // K)
+    pvox = patch[0] * patch[1] * patch[2]
+    for i0 in range(0, len(origins), per_group):
+        group = origins[i0:i0 + per_group]
+        data = torch.empty((len(group) * K, ch) + patch, device=dev)
+        for k, origin in enumerate(group):
+            check(lib().hdf_sw_gather(ptr(image), ch, *size, *origin, *ext, *patch, mask,
+                                      ptr(data) + k * K * ch * pvox * 4, stream_ptr()), "hdf_sw_gather")
+        logits = net(data)[0]
+        if logits.dtype not in _SW_DT:
+            raise _lib.HdfError(f"unsupported logits dtype {logits.dtype}")
+        logits = logits.contiguous()
+        per = K * n_cls * pvox * logits.element_size()
+        for k, origin in enumerate(group):
+            check(lib().hdf_sw_accumulate_tta(_SW_DT[logits.dtype], ptr(logits) + k * per, mask, n_cls, *ext, *patch,
+                                              ptr(tab), ptr(floor), ptr(psum), ptr(wsum), *size, *origin, stream_ptr()),
+                  "hdf_sw_accumulate_tta")
+
+
 @torch.no_grad()
-def sliding_window_predict(net, image, patch_size, step_size, return_probabilities=False, window_batch=4):
+def sliding_window_predict(net, image, patch_size, step_size, return_probabilities=False, window_batch=4, *,
+                           importance=None, sigma_scale=1. / 8, mirror_axes=()):
     """image: [C, D, H, W] (numpy or tensor, any device).  Returns the uint8 label volume [D, H, W] on the model's
     device (and the mean class probabilities when asked).
+
+    importance='gaussian' weights every window voxel by the reference's get_gaussian map (sigma = extent * sigma_scale
+    per axis; gaussian_tables), so that a voxel at a window's border counts less than one at its centre; mirror_axes, a
+    subset of the axes (0, 1, 2) of [D, H, W], also runs every window mirrored along each subset of those axes and averages
+    the un-mirrored softmaxes.  With either, a window costs three launches beside its forward (hdf_sw_gather, the forward
+    of its K = 2^len(mirror_axes) variants as one batch, hdf_sw_accumulate_tta), `window_batch // K` windows (at least
+    one) share a forward, and the probabilities returned are prob_sum / weight_sum.  With neither (the defaults) the
+    call is what it was before these options existed, launch for launch.
 
     Reference loop: trainer.py:527-584.  Windows are gathered `window_batch` at a time into ONE forward of the plan
     (the reference runs them one by one).  An axis shorter than the patch yields the reference's clipped window
     (trainer.py:529-541: `ub = x + patch if it fits else the volume's end`); the reference would hand that smaller
     tensor to the net, which HDenseFormer itself cannot take (its position embeddings fix the token grid), so the
     window is zero-padded up to the patch, run, and only the logits over the real voxels are accumulated."""
+    psum, cnt = _sliding_window_sums(net, image, patch_size, step_size, window_batch, importance, sigma_scale, mirror_axes)
+    label = torch.empty(psum.shape[1:], dtype=torch.uint8, device=psum.device)
+    check(lib().hdf_sw_finalize(ptr(psum), ptr(cnt), psum.shape[0], psum[0].numel(), ptr(label), stream_ptr()),
+          "hdf_sw_finalize")
+    if return_probabilities:
+        return label, psum / cnt
+    return label
+
+
+@torch.no_grad()
+def _sliding_window_sums(net, image, patch_size, step_size, window_batch, importance, sigma_scale, mirror_axes):
+    """the two accumulators of sliding_window_predict before the vote: prob_sum [n_cls, D, H, W] and the count (the sum
+    of the weights under an importance map) [D, H, W], fp32 on the model's device"""
+    if importance not in (None, "gaussian"):
+        raise ValueError(f"importance must be None or 'gaussian', got {importance!r}")
+    mask = _mirror_mask(mirror_axes)
     dev = next(net.parameters()).device
     if dev.type != "cuda":
         raise _lib.HdfError("sliding_window_predict needs the model on a GPU (there is no CPU path)")
@@ -57,32 +149,38 @@ def sliding_window_predict(net, image, patch_size, step_size, return_probabiliti
     origins = [(x, y, z) for x in steps[0] for y in steps[1] for z in steps[2]]
     wb = max(1, int(window_batch))
     try:
-        for i0 in range(0, len(origins), wb):
-            group = origins[i0:i0 + wb]
-            if ext == patch:
-                data = torch.stack([image[:, x:x + patch[0], y:y + patch[1], z:z + patch[2]] for x, y, z in group])
-            else:
-                data = torch.zeros((len(group), image.shape[0]) + patch, device=dev)
-                for k, (x, y, z) in enumerate(group):
-                    data[k, :, :ext[0], :ext[1], :ext[2]] = image[:, x:x + ext[0], y:y + ext[1], z:z + ext[2]]
-            logits = net(data.contiguous())[0]
-            if logits.dtype not in _SW_DT:
-                raise _lib.HdfError(f"unsupported logits dtype {logits.dtype}")
-            if ext != patch:
-                logits = logits[:, :, :ext[0], :ext[1], :ext[2]]
-            logits = logits.contiguous()
-            per = logits[0].numel() * logits.element_size()
-            for k, (x, y, z) in enumerate(group):
-                check(lib().hdf_sw_accumulate(_SW_DT[logits.dtype], ptr(logits) + k * per, n_cls, ext[0], ext[1],
-                                              ext[2], ptr(psum), ptr(cnt), size[0], size[1], size[2], x, y, z,
-                                              stream_ptr()), "hdf_sw_accumulate")
+        if importance is None and not mask:
+            _accumulate_plain(net, image, origins, ext, patch, psum, cnt, wb)
+        else:
+            tables = gaussian_tables(ext, sigma_scale) if importance else None
+            _accumulate_tta(net, image.contiguous(), origins, ext, patch, psum, cnt, wb, mask, tables)
     finally:
         net.train(was_training)
-    label = torch.empty(size, dtype=torch.uint8, device=dev)
-    check(lib().hdf_sw_finalize(ptr(psum), ptr(cnt), n_cls, psum[0].numel(), ptr(label), stream_ptr()), "hdf_sw_finalize")
-    if return_probabilities:
-        return label, psum / cnt
-    return label
+    return psum, cnt
+
+
+def _accumulate_plain(net, image, origins, ext, patch, psum, cnt, wb):
+    """the window loop without options: `wb` windows per forward, one hdf_sw_accumulate per window"""
+    dev, n_cls, size = image.device, psum.shape[0], tuple(psum.shape[1:])
+    for i0 in range(0, len(origins), wb):
+        group = origins[i0:i0 + wb]
+        if ext == patch:
+            data = torch.stack([image[:, x:x + patch[0], y:y + patch[1], z:z + patch[2]] for x, y, z in group])
+        else:
+            data = torch.zeros((len(group), image.shape[0]) + patch, device=dev)
+            for k, (x, y, z) in enumerate(group):
+                data[k, :, :ext[0], :ext[1], :ext[2]] = image[:, x:x + ext[0], y:y + ext[1], z:z + ext[2]]
+        logits = net(data.contiguous())[0]
+        if logits.dtype not in _SW_DT:
+            raise _lib.HdfError(f"unsupported logits dtype {logits.dtype}")
+        if ext != patch:
+            logits = logits[:, :, :ext[0], :ext[1], :ext[2]]
+        logits = logits.contiguous()
+        per = logits[0].numel() * logits.element_size()
+        for k, (x, y, z) in enumerate(group):
+            check(lib().hdf_sw_accumulate(_SW_DT[logits.dtype], ptr(logits) + k * per, n_cls, ext[0], ext[1],
+                                          ext[2], ptr(psum), ptr(cnt), size[0], size[1], size[2], x, y, z,
+                                          stream_ptr()), "hdf_sw_accumulate")
 
 
 def _normalize(image, mode, mean=0.0, w=1024.0):

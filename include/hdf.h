@@ -434,6 +434,37 @@ int hdf_sw_accumulate(int dtype, const void* logits, int n_cls, int pd, int ph, 
 int hdf_sw_finalize(const float* prob_sum, const float* count, int n_cls, int64_t voxels, uint8_t* label,
                     hdf_stream stream);
 
+/* ---- the same loop with a Gaussian importance map (SemanticSeg.get_gaussian, trainer.py:620-638, whose use sits
+ * commented out at trainer.py:566-576) and mirror test-time augmentation: three launches per window beside its forward.
+ * A window has the origin (z0,y0,x0) and the clipped extent (ed,eh,ew) = min(size, patch) per axis inside the patch
+ * (Pd,Ph,Pw) the net takes.  mirror_mask: bit 0 = z, bit 1 = y, bit 2 = x; the K = 2^popcount(mask) variants are the
+ * subsets of the mask in ascending order of their 3-bit code m.
+ * hdf_sw_gather: out[k][c][z][y][x] = image[c][z0 + z'][y0 + y'][x0 + x'] with z' = ed-1-z when bit 0 of m is set, else z
+ * (likewise y, x) for z < ed, y < eh, x < ew, and 0 elsewhere: the content is mirrored within the extent and the zero
+ * padding stays at the high end of every axis.  image [channels][D][H][W] fp32; every element of out is written.
+ * hdf_sw_accumulate_tta: logits [K][n_cls][Pd][Ph][Pw] are the net's answers to those K inputs; logits voxel (z,y,x) of
+ * variant m belongs to window voxel (z',y',x').  Per window voxel v at volume offset o: p_c = (1/K) * sum_m softmax_m(c)
+ * (fp32, max-subtracted, e * (1 / sum), m ascending), prob_sum[c][o] += w * p_c, weight_sum[o] += w, each a separate fp32
+ * rounding; the logits are read with the patch's strides, so a clipped window needs no copy.  w = 1 when tables is null;
+ * with mask 0 and no tables the entry computes hdf_sw_accumulate's result in every bit.  Otherwise tables = tz[ed] | ty[eh]
+ * | tx[ew] (device, fp64): per axis of length n, sigma = n * sigma_scale, r = int(4 sigma + 0.5), k[j] =
+ * exp(-0.5 / sigma^2 * j^2) for |j| <= r normalised to sum 1, t[i] = k[i - n/2] where |i - n/2| <= r, else 0 (what
+ * scipy.ndimage.gaussian_filter does to a unit impulse at n/2 along that axis; hdf_rt.inference.gaussian_tables).
+ * w = float(((tz[z] * ty[y]) * tx[x]) / ((tz[ed/2] * ty[eh/2]) * tx[ew/2])), fp64 in this order, one rounding to fp32,
+ * denormal results kept; where that is 0, w = *floor.  This is get_gaussian's map in every bit.
+ * hdf_sw_importance_floor: *floor_out (device) = the smallest non-zero w of the window, an integer minimum over the bit
+ * patterns: the same from call to call, and the host never waits for it.
+ * hdf_sw_finalize votes on the result with weight_sum in the place of count.  Windows are accumulated one after the
+ * other on one stream: no float atomics.  Refused (HDF_ERR_ARG) before anything is launched: n_cls outside 1..8, an
+ * extent below 1 or beyond the patch, a window outside the volume, mirror_mask > 7, tables without floor or floor
+ * without tables, ed + eh + ew > 4096 with tables, 2^31 or more elements in out or voxels in the window. */
+int hdf_sw_gather(const float* image, int channels, int D, int H, int W, int z0, int y0, int x0, int ed, int eh, int ew,
+                  int Pd, int Ph, int Pw, unsigned mirror_mask, float* out, hdf_stream stream);
+int hdf_sw_importance_floor(const double* tables, int ed, int eh, int ew, float* floor_out, hdf_stream stream);
+int hdf_sw_accumulate_tta(int dtype, const void* logits, unsigned mirror_mask, int n_cls, int ed, int eh, int ew, int Pd,
+                          int Ph, int Pw, const double* tables, const float* floor, float* prob_sum, float* weight_sum,
+                          int D, int H, int W, int z0, int y0, int x0, hdf_stream stream);
+
 /* ---- label staging (data_utils/data_loader.py:126-159, To_Tensor): uint8 class map [N][voxels] -> fp32 one-hot
  * [N][n_cls][voxels]; channel z>=1 is (label == z), channel 0 is "no other class" (so values >= n_cls count as
  * background).  Ships 1 byte per voxel over PCIe instead of 4*n_cls. */
