@@ -347,6 +347,24 @@ int hdf_sw_accumulate_tta(int dtype, const void* logits, unsigned mirror_mask, i
   return hdf_launch_sw_accumulate_tta(dtype, logits, mirror_mask, n_cls, ed, eh, ew, Pd, Ph, Pw, tables, floor, prob_sum,
                                       weight_sum, D, H, W, z0, y0, x0, (hipStream_t)stream);
 }
+int hdf_plane_max(const float* image, int planes, int64_t plane_voxels, float* max_out, hdf_stream stream) {
+  HDF_CHECK_ARG(image && max_out, "plane_max: null argument");
+  return hdf_launch_plane_max(image, planes, plane_voxels, max_out, (hipStream_t)stream);
+}
+int hdf_slice_gather(const float* image, int channels, int D, int H, int W, int z0, int nz, int y0, int x0, int eh, int ew,
+                     int Ph, int Pw, unsigned mirror_mask, int norm_mode, const float* plane_max, float* out,
+                     hdf_stream stream) {
+  HDF_CHECK_ARG(image && out, "slice_gather: null argument");
+  return hdf_launch_slice_gather(image, channels, D, H, W, z0, nz, y0, x0, eh, ew, Ph, Pw, mirror_mask, norm_mode, plane_max,
+                                 out, (hipStream_t)stream);
+}
+int hdf_slice_accumulate(int dtype, const void* logits, unsigned mirror_mask, int n_cls, int nz, int eh, int ew, int Ph,
+                         int Pw, const double* tables, float floor, float* prob_sum, float* weight_sum, int D, int H, int W,
+                         int z0, int y0, int x0, hdf_stream stream) {
+  HDF_CHECK_ARG(logits && prob_sum && weight_sum, "slice_accumulate: null argument");
+  return hdf_launch_slice_accumulate(dtype, logits, mirror_mask, n_cls, nz, eh, ew, Ph, Pw, tables, floor, prob_sum,
+                                     weight_sum, D, H, W, z0, y0, x0, (hipStream_t)stream);
+}
 int hdf_onehot_from_labels(const uint8_t* labels, float* onehot, int batch, int n_cls, int64_t voxels,
                            hdf_stream stream) {
   HDF_CHECK_ARG(labels && onehot, "onehot_from_labels: null argument");

@@ -1,4 +1,4 @@
-// The evaluation path (metrics.hip, sw_infer.hip): the on-device Dice metric and the sliding-window inference tail.
+// The evaluation path (metrics.hip, sw_infer.hip, slice_infer.hip): the on-device Dice metric and the sliding-window inference tail.
 #pragma once
 #include "loss.h"  // HDF_CLASS_SLOTS
 
@@ -22,3 +22,11 @@ int hdf_launch_sw_importance_floor(const double* tables, int ed, int eh, int ew,
 int hdf_launch_sw_accumulate_tta(int dtype, const void* logits, unsigned mask, int C, int ed, int eh, int ew, int Pd, int Ph,
                                  int Pw, const double* tables, const float* floor, float* psum, float* wsum, int D, int H,
                                  int W, int z0, int y0, int x0, hipStream_t st);
+// slice_infer.hip: the same around the 2-D model's forward of a group of slices -- the maxima of the volume's planes, the
+// slices' mirrored and normalised copies, and the tail over all of them in one launch
+int hdf_launch_plane_max(const float* image, int planes, int64_t pv, float* max_out, hipStream_t st);
+int hdf_launch_slice_gather(const float* image, int C, int D, int H, int W, int z0, int nz, int y0, int x0, int eh, int ew,
+                            int Ph, int Pw, unsigned mask, int mode, const float* plane_max, float* out, hipStream_t st);
+int hdf_launch_slice_accumulate(int dtype, const void* logits, unsigned mask, int C, int nz, int eh, int ew, int Ph, int Pw,
+                                const double* tables, float floor, float* psum, float* wsum, int D, int H, int W, int z0,
+                                int y0, int x0, hipStream_t st);

@@ -4,30 +4,9 @@
 //
 // Reference: the importance map is SemanticSeg.get_gaussian (trainer.py:620-638), whose use sits commented out beside the
 // accumulation (trainer.py:566-576); include/hdf.h states the arithmetic.
-#include "metrics.h"
-
-// every rounding below is written out (the one fused multiply-add is spelled __builtin_fmaf)
-#pragma clang fp contract(off)
+#include "sw_common.h"   // the launch shape, sw_variant (here bit 0 = z, 1 = y, 2 = x), sw_softmax; fp contract(off)
 
 namespace {
-constexpr int SW_MAXC = HDF_CLASS_SLOTS;
-constexpr int SW_MAX_TABLE = 4096;   // doubles of the three per-axis tables held in LDS (32 KiB)
-constexpr int SW_THREADS = 256;
-constexpr int SW_MAX_BLOCKS = 4096;
-
-// code of the k-th mirror variant (bit 0 = z, 1 = y, 2 = x): the subsets of `mask` in ascending order of their code, i.e.
-// the bits of k dealt out to the set bits of mask from the lowest up
-__device__ __forceinline__ unsigned sw_variant(unsigned mask, unsigned k) {
-  unsigned m = 0;
-#pragma unroll
-  for (unsigned b = 0; b < 3; b++)
-    if ((mask >> b) & 1u) {
-      m |= (k & 1u) << b;
-      k >>= 1;
-    }
-  return m;
-}
-
 // out[k][c][z][y][x] = the window's voxel mirrored WITHIN the clipped extent (flip the content, then pad): zeros beyond
 // the extent stay at the high end of every axis.  One thread per VEC consecutive output elements of a row (4 in one
 // store where the row length and the address allow it: the index arithmetic, not the traffic, bounds the scalar form);
@@ -98,27 +77,6 @@ __global__ __launch_bounds__(SW_THREADS) void sw_floor_kernel(const double* __re
   if (lo != 0xffffffffu) atomicMin(&blk, lo);
   __syncthreads();
   if (threadIdx.x == 0 && blk != 0xffffffffu) atomicMin(floor_bits, blk);
-}
-
-// fp32 softmax over the classes of one voxel, as sw_accumulate_kernel (metrics.hip) takes it: v[c] = exp(l_c - max),
-// returns 1 / sum; the softmax is v[c] * that
-template <typename T>
-__device__ __forceinline__ float sw_softmax(const T* __restrict__ p, int64_t plane, int C, float* v) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < SW_MAXC; c++)
-    if (c < C) {
-      v[c] = ST<T>::ld(p + c * plane);
-      mx = fmaxf(mx, v[c]);
-    }
-  float sum = 0.f;
-#pragma unroll
-  for (int c = 0; c < SW_MAXC; c++)
-    if (c < C) {
-      v[c] = expf(v[c] - mx);
-      sum += v[c];
-    }
-  return 1.f / sum;
 }
 
 // One thread per voxel of the clipped window.  The K variants of the logits [K][C][Pd][Ph][Pw] are read at their mirrored
@@ -195,7 +153,6 @@ int sw_check_patch(const char* what, int ed, int eh, int ew, int Pd, int Ph, int
   HDF_CHECK_ARG(mask < 8u, "%s: mirror_mask %u (bit 0 = z, 1 = y, 2 = x: at most 7)", what, mask);
   return HDF_OK;
 }
-unsigned sw_grid(int64_t n) { return (unsigned)std::min<int64_t>(ceil_div64(n, SW_THREADS), SW_MAX_BLOCKS); }
 }  // namespace
 
 int hdf_launch_sw_gather(const float* image, int C, int D, int H, int W, int z0, int y0, int x0, int ed, int eh, int ew,

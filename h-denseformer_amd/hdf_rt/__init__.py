@@ -8,7 +8,7 @@ _SURFACE = ("cal_score", "multi_dice", "multi_hd", "multi_jc", "multi_vs", "surf
             "asd_from_result", "asd_scores", "cal_asd", "multi_asd")
 _COMPONENTS = ("connected_components", "component_table", "component_stats", "keep_largest_component",
                "remove_small_components")
-_INFERENCE = ("cal_steps", "gaussian_tables", "sliding_window_predict")
+_INFERENCE = ("cal_steps", "gaussian_tables", "sliding_window_predict", "slice_predict")
 
 
 def __getattr__(name):

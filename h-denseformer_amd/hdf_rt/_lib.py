@@ -87,6 +87,9 @@ _PROTOS = {
     "hdf_sw_gather": (_i, [_vp] + [_i] * 13 + [C.c_uint, _vp, _vp]),
     "hdf_sw_importance_floor": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "hdf_sw_accumulate_tta": (_i, [_i, _vp, C.c_uint] + [_i] * 7 + [_vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
+    "hdf_plane_max": (_i, [_vp, _i, _i64, _vp, _vp]),
+    "hdf_slice_gather": (_i, [_vp] + [_i] * 12 + [C.c_uint, _i, _vp, _vp, _vp]),
+    "hdf_slice_accumulate": (_i, [_i, _vp, C.c_uint] + [_i] * 6 + [_vp, _f, _vp, _vp] + [_i] * 6 + [_vp]),
     "hdf_onehot_from_labels": (_i, [_vp, _vp, _i, _i, _i64, _vp]),
     "hdf_augment_3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _pd, _i, _i, _vp, _vp, _vp, _vp]),
     "hdf_augment_2d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _pd, _vp, _vp, _vp, _vp, _vp]),

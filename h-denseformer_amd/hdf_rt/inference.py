@@ -4,7 +4,8 @@ full-size fp32 accumulators with indexed torch ops and finally argmaxes a softma
 moves it to the host.  Here the per-window tail (softmax + accumulate + count) is ONE HIP kernel reading the logits
 once, the vote is one kernel writing a uint8 map; the model is the MI355X-native HDenseFormer.  No CPU fallback.
 Two options the reference only sketches stay on the device as well: its Gaussian importance map (get_gaussian,
-trainer.py:620-638, bit for bit) and mirror test-time augmentation (csrc/sw_infer.hip)."""
+trainer.py:620-638, bit for bit) and mirror test-time augmentation (csrc/sw_infer.hip).  slice_predict does the same for
+the 2-D model, slice by slice (eval.py:125-230; csrc/slice_infer.hip), and returns the same uint8 map."""
 import numpy as np
 import torch
 
@@ -181,6 +182,120 @@ def _accumulate_plain(net, image, origins, ext, patch, psum, cnt, wb):
             check(lib().hdf_sw_accumulate(_SW_DT[logits.dtype], ptr(logits) + k * per, n_cls, ext[0], ext[1],
                                           ext[2], ptr(psum), ptr(cnt), size[0], size[1], size[2], x, y, z,
                                           stream_ptr()), "hdf_sw_accumulate")
+
+
+_NORM_MODE = {None: 0, "mr": 1, "max": 2}
+
+
+def _plane_mirror_mask(mirror_axes):
+    """axes of the plane [H, W] -> the C ABI's mask of the slice entries (bit 0 = y, 1 = x)"""
+    mask = 0
+    for a in tuple(mirror_axes):
+        if isinstance(a, bool) or not isinstance(a, (int, np.integer)) or a not in (0, 1) or mask >> int(a) & 1:
+            raise ValueError(f"mirror_axes must be a subset of (0, 1) without repeats, got {mirror_axes!r}")
+        mask |= 1 << int(a)
+    return mask
+
+
+def plane_floor(tables):
+    """the smallest non-zero weight of the plane's importance map: float((ty[y] * tx[x]) / (ty[eh/2] * tx[ew/2])) over the
+    window, from the two host tables of gaussian_tables((eh, ew)) -- what hdf_slice_accumulate takes as `floor`"""
+    ty, tx = tables
+    raw = ((ty[:, None] * tx[None, :]) / (ty[len(ty) // 2] * tx[len(tx) // 2])).astype(np.float32)
+    return float(raw[raw != 0].min())
+
+
+@torch.no_grad()
+def slice_predict(net, volume, slice_batch=24, *, normalize="mr", step_size=None, importance=None, sigma_scale=1. / 8,
+                  mirror_axes=(), return_probabilities=False):
+    """Slice-wise inference of a volume with the 2-D model (reference: eval.py:125-230, which normalises every plane,
+    pushes the slices through the net, takes the softmax, stacks to [n_cls, D, H, W] and argmaxes on the host).
+    volume: [C, D, H, W] (numpy or tensor, any device).  Returns the uint8 label volume [D, H, W] on the model's device --
+    what sliding_window_predict returns for the 3-D model -- and, when asked, prob_sum / weight_sum as [n_cls, D, H, W],
+    the array predict_process returns after its transpose.
+
+    normalize: "mr" is MRNormalize plane by plane (data_loader.py:39-50, the validation chain of trainer.py:173-176),
+    "max" is eval.py's Normalize_2d (the same without the clamp of negatives), None takes the planes as they are; the
+    maximum is that of the whole plane [H, W] of a channel.  In the plane the windows follow sliding_window_predict's
+    rules: an axis no longer than the model's image_size gives the origin 0 and a zero-padded clipped window, a longer
+    one is covered by cal_steps with step_size (default: half the patch, the ratio of config.py:118-119).
+    importance='gaussian' weights a window's pixels by get_gaussian((eh, ew)) (trainer.py:620-638); mirror_axes, a subset
+    of the axes (0, 1) of the plane, also runs every slice mirrored along each subset of them and averages the
+    un-mirrored softmaxes.  In-plane origins outer, slices inner, in groups of max(1, slice_batch // K), K =
+    2^len(mirror_axes): a group costs one hdf_slice_gather, one forward of [slices x K variants] and one
+    hdf_slice_accumulate; a call adds one hdf_plane_max and one hdf_sw_finalize.  Nothing waits on the host.  The
+    defaults with normalize="max" on planes of the model's size are eval.py:208-230."""
+    psum, wsum = _slice_sums(net, volume, slice_batch, normalize, step_size, importance, sigma_scale, mirror_axes)
+    label = torch.empty(psum.shape[1:], dtype=torch.uint8, device=psum.device)
+    check(lib().hdf_sw_finalize(ptr(psum), ptr(wsum), psum.shape[0], psum[0].numel(), ptr(label), stream_ptr()),
+          "hdf_sw_finalize")
+    if return_probabilities:
+        return label, psum / wsum
+    return label
+
+
+@torch.no_grad()
+def _slice_sums(net, volume, slice_batch, normalize, step_size, importance, sigma_scale, mirror_axes):
+    """the two accumulators of slice_predict before the vote: prob_sum [n_cls, D, H, W] and weight_sum [D, H, W], fp32 on
+    the model's device"""
+    if importance not in (None, "gaussian"):
+        raise ValueError(f"importance must be None or 'gaussian', got {importance!r}")
+    if normalize not in _NORM_MODE:
+        raise ValueError(f"normalize must be 'mr', 'max' or None, got {normalize!r}")
+    mask = _plane_mirror_mask(mirror_axes)
+    from models.HDenseFormer_2D import HDenseFormer_2D
+    if not isinstance(net, HDenseFormer_2D):
+        raise ValueError(f"slice_predict takes a HDenseFormer_2D (sliding_window_predict runs the 3-D model), got "
+                         f"{type(net).__name__}")
+    dev = next(net.parameters()).device
+    if dev.type != "cuda":
+        raise _lib.HdfError("slice_predict needs the model on a GPU (there is no CPU path)")
+    volume = torch.as_tensor(volume).float().to(dev).contiguous()
+    if volume.dim() != 4 or volume.shape[0] != net.in_channels:
+        raise ValueError(f"volume must be [{net.in_channels}, D, H, W], got {tuple(volume.shape)}")
+    ch, depth = int(volume.shape[0]), int(volume.shape[1])
+    plane = tuple(int(s) for s in volume.shape[2:])
+    patch = tuple(int(p) for p in net.image_size)
+    step = tuple(max(1, p // 2) for p in patch) if step_size is None else tuple(int(s) for s in step_size)
+    if len(step) != 2 or min(step) < 1:
+        raise ValueError(f"step_size must be two positive steps (y, x), got {step_size!r}")
+    ext = tuple(min(s, p) for s, p in zip(plane, patch))          # clipped window extent, as in the 3-D loop
+    K = 1 << bin(mask).count("1")
+    per_group = max(1, int(slice_batch) // K)
+    n_cls, mode = net.n_cls, _NORM_MODE[normalize]
+    tab, floor = None, 0.0
+    if importance:
+        tables = gaussian_tables(ext, sigma_scale)
+        tab, floor = torch.from_numpy(np.concatenate(tables)).to(dev), plane_floor(tables)
+    pmax = None
+    if mode:
+        pmax = torch.empty(ch * depth, device=dev)
+        check(lib().hdf_plane_max(ptr(volume), ch * depth, plane[0] * plane[1], ptr(pmax), stream_ptr()), "hdf_plane_max")
+    psum = torch.zeros((n_cls, depth) + plane, device=dev)
+    wsum = torch.zeros((depth,) + plane, device=dev)
+    steps = cal_steps(plane, patch, step)
+    was_training = net.training
+    if was_training:          # (a walk over the model's modules, about a millisecond: not for a net already in eval mode)
+        net.eval()
+    try:
+        for y0 in steps[0]:
+            for x0 in steps[1]:
+                for z0 in range(0, depth, per_group):
+                    nz = min(per_group, depth - z0)
+                    data = torch.empty((nz * K, ch) + patch, device=dev)
+                    check(lib().hdf_slice_gather(ptr(volume), ch, depth, *plane, z0, nz, y0, x0, *ext, *patch, mask, mode,
+                                                 ptr(pmax), ptr(data), stream_ptr()), "hdf_slice_gather")
+                    logits = net(data)[0]
+                    if logits.dtype not in _SW_DT:
+                        raise _lib.HdfError(f"unsupported logits dtype {logits.dtype}")
+                    logits = logits.contiguous()
+                    check(lib().hdf_slice_accumulate(_SW_DT[logits.dtype], ptr(logits), mask, n_cls, nz, *ext, *patch,
+                                                     ptr(tab), floor, ptr(psum), ptr(wsum), depth, *plane, z0, y0, x0,
+                                                     stream_ptr()), "hdf_slice_accumulate")
+    finally:
+        if was_training:
+            net.train()
+    return psum, wsum
 
 
 def _normalize(image, mode, mean=0.0, w=1024.0):

@@ -465,6 +465,42 @@ int hdf_sw_accumulate_tta(int dtype, const void* logits, unsigned mirror_mask, i
                           int Ph, int Pw, const double* tables, const float* floor, float* prob_sum, float* weight_sum,
                           int D, int H, int W, int z0, int y0, int x0, hdf_stream stream);
 
+/* ---- slice-wise volume inference for the 2-D model (eval.py:125-230: normalise every plane, push the slices through
+ * the net, softmax, stack to [n_cls][D][H][W], argmax): the launches around the forward of a group of slices.  image is
+ * the volume [channels][D][H][W] fp32.  An in-plane window has the origin (y0,x0) and the clipped extent (eh,ew) =
+ * min(size, patch) per axis inside the patch (Ph,Pw) the net takes, and covers the slices z0 .. z0+nz-1.  mirror_mask:
+ * bit 0 = y, bit 1 = x; the K = 2^popcount(mask) variants are the subsets of the mask in ascending order of their code m.
+ * hdf_plane_max: max_out[p] = the maximum of plane p of `planes` fp32 planes of plane_voxels each (for a volume:
+ * planes = channels * D, p = c * D + z).  Exact: a maximum has no rounding.  The inputs must be finite (a NaN is
+ * skipped, not propagated); of zeros of both signs either may come back.  One workgroup forms one plane's maximum: the
+ * same from call to call.
+ * hdf_slice_gather: out[s][k][c][y][x] = f(image[c][z0 + s][y0 + y'][x0 + x']) with y' = eh-1-y when bit 0 of m is set,
+ * else y (likewise x) for y < eh, x < ew, and 0 elsewhere: slices outer, a slice's K variants side by side, the content
+ * mirrored within the extent, the zero padding at the high end of both axes; every element of out is written.
+ * norm_mode 0: f(v) = v.  1: MRNormalize plane by plane (data_utils/data_loader.py:39-50, the validation chain of
+ * trainer.py:173-176): v / max when max != 0, else v, then negatives to 0.  2: Normalize_2d (eval.py:112-123): the same
+ * without the clamp.  max = plane_max[c * D + z0 + s], the maximum of the whole plane (hdf_plane_max), not of the
+ * window; the division is one IEEE fp32 division, as in hdf_normalize_mr.
+ * hdf_slice_accumulate: logits [nz][K][n_cls][Ph][Pw] are the net's answers to that batch.  Per slice the arithmetic is
+ * hdf_sw_accumulate_tta's on a window of depth 1, word for word: p_c = (1/K) * sum_m softmax_m(c) (fp32, max-subtracted,
+ * e * (1 / sum), m ascending), prob_sum[c][o] += w * p_c, weight_sum[o] += w, each a separate fp32 rounding, the logits
+ * read with the patch's strides; without mirroring and tables it is hdf_sw_accumulate's result in every bit.  w = 1 when
+ * tables is null.  Otherwise tables = ty[eh] | tx[ew] (device, fp64; hdf_rt.inference.gaussian_tables((eh, ew))), w =
+ * float((ty[y] * tx[x]) / (ty[eh/2] * tx[ew/2])), fp64, one rounding to fp32, denormal results kept; where that is 0,
+ * w = floor, which the caller forms on the host from the same tables: the smallest non-zero w of the window.  This is
+ * get_gaussian((eh, ew)) (trainer.py:620-638) in every bit.  One launch covers the nz slices; their voxels are disjoint:
+ * no float atomics.  hdf_sw_finalize votes on the result.
+ * Refused (HDF_ERR_ARG) before anything is launched: n_cls outside 1..8, nz < 1 or z0 + nz > D, a window outside the
+ * plane, an extent below 1 or beyond the patch, mirror_mask > 3, norm_mode outside 0..2 or non-zero without plane_max,
+ * eh + ew > 4096 with tables, 2^31 or more elements in out or voxels in the launch. */
+int hdf_plane_max(const float* image, int planes, int64_t plane_voxels, float* max_out, hdf_stream stream);
+int hdf_slice_gather(const float* image, int channels, int D, int H, int W, int z0, int nz, int y0, int x0, int eh, int ew,
+                     int Ph, int Pw, unsigned mirror_mask, int norm_mode, const float* plane_max, float* out,
+                     hdf_stream stream);
+int hdf_slice_accumulate(int dtype, const void* logits, unsigned mirror_mask, int n_cls, int nz, int eh, int ew, int Ph,
+                         int Pw, const double* tables, float floor, float* prob_sum, float* weight_sum, int D, int H, int W,
+                         int z0, int y0, int x0, hdf_stream stream);
+
 /* ---- label staging (data_utils/data_loader.py:126-159, To_Tensor): uint8 class map [N][voxels] -> fp32 one-hot
  * [N][n_cls][voxels]; channel z>=1 is (label == z), channel 0 is "no other class" (so values >= n_cls count as
  * background).  Ships 1 byte per voxel over PCIe instead of 4*n_cls. */

@@ -7,6 +7,7 @@ bounded host-side restatement of what the reference does for the same call (nump
   python tools/bench_rows.py transforms2d                       (the full 2-D transform list row alone)
   python tools/bench_rows.py resize3d                           (the CropResize row alone)
   python tools/bench_rows.py components                         (the connected-component rows alone)
+  python tools/bench_rows.py slice2d                            (the slice-wise 2-D inference row alone)
 """
 import json
 import os
@@ -279,6 +280,65 @@ def components_row(shapes=((144, 144, 144), (448, 512, 512)), connectivity=26):
         torch.cuda.empty_cache()
 
 
+def slice2d_row(C=3, D=24, S=384, slice_batch=24):
+    """slice_predict of HDenseFormer_2D_32(3, 2, (384, 384), 24) on a 3 x 24 x 384^2 volume (the reference's 2-D workload,
+    config.py:69-77; bf16, one in-plane window, no mirroring: one hdf_plane_max, one hdf_slice_gather, one forward of 24
+    slices, one hdf_slice_accumulate, one hdf_sw_finalize), next to two figures of the same run: the eval forward of the 24
+    slices alone, and the same volume through the per-window entries driven with windows of depth 1 -- a copy (the
+    normalisation is in place), MRNormalize per plane as chunked mr_normalize_ calls (64 planes a call), one hdf_sw_gather
+    and one hdf_sw_accumulate_tta per slice, the same forward and vote.  Medians of 30 calls after 5, with the extremes."""
+    from hdf_rt._lib import check, lib, ptr, stream_ptr
+    from models.HDenseFormer_2D import HDenseFormer_2D_32
+    gen = torch.Generator().manual_seed(16)
+    net = HDenseFormer_2D_32(C, 2, (S, S), 24).to(DEV).eval()
+    net.compute_dtype = "bf16"
+    vol = (torch.rand(C, D, S, S, generator=gen) * 900).to(DEV)
+    x = torch.rand(slice_batch, C, S, S, generator=gen).to(DEV)
+    pv, st = S * S, stream_ptr()
+
+    def per_window():
+        v = vol.clone()
+        planes = v.view(C * D, S, S)
+        for i in range(0, C * D, 64):
+            inference.mr_normalize_(planes[i:i + 64])
+        psum, wsum = torch.zeros((2, D, S, S), device=DEV), torch.zeros((D, S, S), device=DEV)
+        for z0 in range(0, D, slice_batch):
+            nz = min(slice_batch, D - z0)
+            data = torch.empty((nz, C, S, S), device=DEV)
+            for k in range(nz):
+                check(lib().hdf_sw_gather(ptr(v), C, D, S, S, z0 + k, 0, 0, 1, S, S, 1, S, S, 0, ptr(data) + k * C * pv * 4, st),
+                      "hdf_sw_gather")
+            logits = net(data)[0].contiguous()
+            per = 2 * pv * logits.element_size()
+            for k in range(nz):
+                check(lib().hdf_sw_accumulate_tta(inference._SW_DT[logits.dtype], ptr(logits) + k * per, 0, 2, 1, S, S, 1, S, S,
+                                                  None, None, ptr(psum), ptr(wsum), D, S, S, z0 + k, 0, 0, st),
+                      "hdf_sw_accumulate_tta")
+        label = torch.empty((D, S, S), dtype=torch.uint8, device=DEV)
+        check(lib().hdf_sw_finalize(ptr(psum), ptr(wsum), 2, D * pv, ptr(label), st), "hdf_sw_finalize")
+        return label
+
+    def timed(fn):
+        for _ in range(5):
+            fn()
+        ts = sorted(gpu_ms(fn, reps=1, warm=0) for _ in range(30))
+        return {"median_ms": ts[15], "min_ms": ts[0], "max_ms": ts[-1]}
+
+    with torch.no_grad():
+        same = bool(torch.equal(inference.slice_predict(net, vol, slice_batch), per_window()))
+        a = timed(lambda: inference.slice_predict(net, vol, slice_batch))
+        b = timed(lambda: net(x))
+        c = timed(per_window)
+    emit(row="slice2d", config=f"HDenseFormer_2D_32({C}, 2, ({S}, {S}), 24) bf16, {C}x{D}x{S}^2 fp32 volume, slice_batch {slice_batch}, "
+         "normalize 'mr', no importance, no mirroring", slice_predict=a, forward_alone=b, per_window_entries=c,
+         library_launches_beside_the_forward={"slice_predict": 4, "per_window_entries": 3 * (-(-C * D // 64)) + 2 * D + 1},
+         labels_equal=same, tail_ms={"slice_predict": a["median_ms"] - b["median_ms"],
+                                     "per_window_entries": c["median_ms"] - b["median_ms"]})
+
+
+if sys.argv[1:] == ["slice2d"]:
+    slice2d_row()
+    sys.exit(0)
 if sys.argv[1:] == ["components"]:
     components_row()
     sys.exit(0)
@@ -356,6 +416,8 @@ emit(row="8f-3 mr_normalize_", config=f"{C}x{S}^3 fp32 in place (clone time {ms0
 augment_row()
 augment2d_row()
 transforms2d_row()
+slice2d_row()
+torch.cuda.empty_cache()
 
 # ---- 8f-2: sliding-window inference
 from models.HDenseFormer import HDenseFormer
