@@ -1,5 +1,5 @@
 // Process state (last error, compute-unit budget) and the one-to-one C ABI wrappers of the operator launchers: losses,
-// metrics, surface distances, connected components, normalisation, sliding window, augmentation, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
+// metrics, surface distances, connected components, binary morphology, normalisation, sliding window, augmentation, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
 #include <atomic>
 #include <algorithm>
 #include <cstdarg>
@@ -11,6 +11,7 @@
 #include "conv_igemm.h"
 #include "loss.h"
 #include "metrics.h"
+#include "morphology.h"
 #include "optim.h"
 #include "surface.h"
 #include "transformer.h"
@@ -308,6 +309,53 @@ int hdf_cc_filter(const uint8_t* volume, const int32_t* ids, int D, int H, int W
                 "components: filter: out overlaps volume without being volume");
   return hdf_launch_cc_filter(volume, ids, D, H, W, min_size, keep_largest, out, (unsigned long long*)result, workspace,
                               (hipStream_t)stream);
+}
+// binary morphology (morphology.hip)
+static int morph_check_buffers(const char* who, const uint8_t* volume, const uint8_t* out, const uint64_t* result,
+                               const void* workspace, int64_t workspace_bytes, int64_t need, int64_t V) {
+  HDF_CHECK_ARG(volume && out && result && workspace, "morphology: %s: null argument", who);
+  HDF_CHECK_ARG(workspace_bytes >= need, "morphology: %s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes,
+                (long long)need);
+  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "morphology: %s: workspace not aligned to 8 bytes", who);
+  HDF_CHECK_ARG(out == volume || !hdf_cc_overlap(out, V, volume, V), "morphology: %s: out overlaps volume without being volume",
+                who);
+  HDF_CHECK_ARG(!hdf_cc_overlap(workspace, need, volume, V) && !hdf_cc_overlap(workspace, need, out, V) &&
+                    !hdf_cc_overlap(workspace, need, result, 16),
+                "morphology: %s: workspace overlaps volume, out or result", who);
+  HDF_CHECK_ARG(!hdf_cc_overlap(result, 16, volume, V) && !hdf_cc_overlap(result, 16, out, V),
+                "morphology: %s: result overlaps volume or out", who);
+  return HDF_OK;
+}
+int64_t hdf_morph_workspace_bytes(int D, int H, int W) {
+  if (hdf_morph_check_dims("workspace_bytes", D, H, W) != HDF_OK) return -1;
+  return hdf_morph_ws_bytes(D, H, W);
+}
+int hdf_morph(const uint8_t* volume, int label, int op, int connectivity, int iterations, int border_value, int mode, int D,
+              int H, int W, uint8_t* out, uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream) {
+  HDF_TRY(hdf_morph_check_dims("morph", D, H, W));
+  HDF_CHECK_ARG(op == HDF_MORPH_DILATE || op == HDF_MORPH_ERODE || op == HDF_MORPH_OPEN || op == HDF_MORPH_CLOSE,
+                "morphology: morph: op %d (HDF_MORPH_DILATE, _ERODE, _OPEN or _CLOSE)", op);
+  HDF_TRY(hdf_morph_check_mask_args("morph", label, connectivity, mode));
+  HDF_CHECK_ARG(iterations >= 1 && iterations <= HDF_MORPH_MAX_ITER, "morphology: morph: iterations %d (1..%d)", iterations,
+                HDF_MORPH_MAX_ITER);
+  HDF_CHECK_ARG(border_value == 0 || border_value == 1, "morphology: morph: border_value %d (0 or 1)", border_value);
+  HDF_TRY(morph_check_buffers("morph", volume, out, result, workspace, workspace_bytes, hdf_morph_ws_bytes(D, H, W),
+                              (int64_t)D * H * W));
+  return hdf_launch_morph(volume, label, op, connectivity, iterations, border_value, mode, D, H, W, out,
+                          (unsigned long long*)result, workspace, (hipStream_t)stream);
+}
+int64_t hdf_fill_holes_workspace_bytes(int D, int H, int W) {
+  if (hdf_morph_check_dims("workspace_bytes", D, H, W) != HDF_OK) return -1;
+  return hdf_fill_holes_ws_bytes(D, H, W);
+}
+int hdf_fill_holes(const uint8_t* volume, int label, int connectivity, int mode, int D, int H, int W, uint8_t* out,
+                   uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream) {
+  HDF_TRY(hdf_morph_check_dims("fill_holes", D, H, W));
+  HDF_TRY(hdf_morph_check_mask_args("fill_holes", label, connectivity, mode));
+  HDF_TRY(morph_check_buffers("fill_holes", volume, out, result, workspace, workspace_bytes, hdf_fill_holes_ws_bytes(D, H, W),
+                              (int64_t)D * H * W));
+  return hdf_launch_fill_holes(volume, label, connectivity, mode, D, H, W, out, (unsigned long long*)result, workspace,
+                               (hipStream_t)stream);
 }
 int64_t hdf_normalize_workspace_bytes(int channels) { return (int64_t)hdf_norm_ws_bytes(channels); }
 int hdf_normalize_mr(float* image, int channels, int64_t voxels, void* workspace, hdf_stream stream) {

@@ -8,6 +8,8 @@ _SURFACE = ("cal_score", "multi_dice", "multi_hd", "multi_jc", "multi_vs", "surf
             "asd_from_result", "asd_scores", "cal_asd", "multi_asd")
 _COMPONENTS = ("connected_components", "component_table", "component_stats", "keep_largest_component",
                "remove_small_components")
+_MORPHOLOGY = ("binary_dilation", "binary_erosion", "binary_opening", "binary_closing", "binary_fill_holes", "morph_class",
+               "fill_class_holes")
 _INFERENCE = ("cal_steps", "gaussian_tables", "sliding_window_predict", "slice_predict")
 
 
@@ -25,8 +27,12 @@ def __getattr__(name):
     if name in _COMPONENTS:
         from . import components
         return getattr(components, name)
+    if name in _MORPHOLOGY:
+        from . import morphology
+        return getattr(morphology, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def __dir__():
-    return sorted(list(globals()) + list(_AUGMENT) + list(_SURFACE) + list(_COMPONENTS) + list(_INFERENCE))
+    return sorted(list(globals()) + list(_AUGMENT) + list(_SURFACE) + list(_COMPONENTS) + list(_MORPHOLOGY) +
+                  list(_INFERENCE))

@@ -43,6 +43,8 @@ def clear_workspaces():
     _mm_workspaces.clear()
     from . import components
     components.clear_workspaces()      # the connected-component entries keep a cache of their own
+    from . import morphology
+    morphology.clear_workspaces()      # and so do the morphology entries
 
 
 def _volume(a, what):

@@ -413,6 +413,53 @@ int hdf_cc_table(const uint8_t* volume, const int32_t* ids, const float* score, 
 int hdf_cc_filter(const uint8_t* volume, const int32_t* ids, int D, int H, int W, int64_t min_size, int keep_largest,
                   uint8_t* out, uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream);
 
+/* ---- binary morphology of a label map (the reference has no such code: its users run scipy.ndimage.binary_dilation /
+ * binary_erosion / binary_opening / binary_closing / binary_fill_holes on the host).  volume: uint8 [D][H][W] on the device.
+ *   input mask   label = 0: every non-zero voxel is foreground; k in 1..255: only the voxels equal to k are.
+ *   element      connectivity 6 / 18 / 26 = scipy's generate_binary_structure(3, c) with c = 1 / 2 / 3: the offsets
+ *            (dz, dy, dx) in {-1, 0, 1}^3 with |dz| + |dy| + |dx| <= c.  A depth-1 volume is the 2-D case: the z axis does
+ *            not exist, there are no z neighbours and no z border, 6 / 18 / 26 are the 4- / 8- / 8-neighbourhood.
+ *   one step     a voxel outside the volume reads as border_value (0 or 1, scipy's parameter).  Dilate: a voxel is set if
+ *            any voxel under the element is set.  Erode: a voxel is set if all voxels under the element are set.
+ *   iterations   n steps, n in 1..256 (n < 1 is scipy's "until nothing changes" and is refused).
+ *   op           HDF_MORPH_DILATE, HDF_MORPH_ERODE; HDF_MORPH_OPEN = n erosions, then n dilations; HDF_MORPH_CLOSE = n
+ *            dilations, then n erosions.  Both halves use the same element and the same border_value: with border_value
+ *            = 0 closing erodes an object that touches a face, as scipy's does.
+ *   fill holes   new mask = input mask OR every background voxel whose background component, taken under `connectivity`
+ *            (scipy's default: 6), touches no face of the volume (no edge, in the 2-D case) =
+ *            binary_fill_holes(mask, generate_binary_structure(3, c)).
+ *   mode         HDF_MORPH_MASK: out[v] = 1 where the new mask is set, else 0.  HDF_MORPH_MAP (needs label >= 1): out[v] =
+ *            0 where a voxel left the mask, label where a voxel joined the mask and held 0, volume[v] everywhere else -- a
+ *            voxel of another class is never overwritten, so the result is still a class map.  out may be volume (in
+ *            place), and may not overlap it otherwise.
+ *   result       [2] uint64 = the voxels of the new mask, the voxels where the new mask differs from the input mask.  Both
+ *            are counted on masks, whatever the mode.
+ * hdf_morph packs the mask to one bit a voxel (32-bit words along x, every row on a word), runs every step on packed words
+ * between the two packed buffers of its workspace (2 * ceil(W / 32) * 4 bytes a row, each buffer rounded up to 256 bytes:
+ * 0.25 byte a voxel when W is a multiple of 32) and unpacks once.  hdf_fill_holes labels the complement of the mask with
+ * the kernels of hdf_cc_label; its workspace holds the complement map, the id map, a flag per id and that labelling's own
+ * workspace, about 11 bytes a voxel.
+ * Only integer operations and integer atomics are used: every output is exact and the same from call to call.  No kernel
+ * waits on another workgroup (csrc/morphology.hip).  All pointers are device memory, the kernels are ordered on `stream`,
+ * nothing waits on the host, and a workspace may be reused by the next call on the same stream without clearing.  Refused
+ * (HDF_ERR_ARG, message "morphology: ...") before anything is launched: a dimension outside 1..1024, D*H*W >= 2^31,
+ * connectivity not 6 / 18 / 26, label outside 0..255, iterations outside 1..256, border_value not 0 / 1, an unknown op or
+ * mode, HDF_MORPH_MAP with label = 0, a null required pointer, a workspace below hdf_morph_workspace_bytes(D, H, W) or
+ * hdf_fill_holes_workspace_bytes(D, H, W) (-1 for refused dimensions) or not aligned to 8 bytes, out overlapping volume
+ * without being volume, the workspace or result overlapping volume, out or each other. */
+#define HDF_MORPH_DILATE 0
+#define HDF_MORPH_ERODE 1
+#define HDF_MORPH_OPEN 2
+#define HDF_MORPH_CLOSE 3
+#define HDF_MORPH_MASK 0
+#define HDF_MORPH_MAP 1
+int64_t hdf_morph_workspace_bytes(int D, int H, int W);
+int hdf_morph(const uint8_t* volume, int label, int op, int connectivity, int iterations, int border_value, int mode, int D,
+              int H, int W, uint8_t* out, uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream);
+int64_t hdf_fill_holes_workspace_bytes(int D, int H, int W);
+int hdf_fill_holes(const uint8_t* volume, int label, int connectivity, int mode, int D, int H, int W, uint8_t* out,
+                   uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream);
+
 /* ---- input normalisation on the device, in place on one fp32 sample [channels][voxels] -----------------------
  * hdf_normalize_mr: MRNormalize (data_utils/data_loader.py:39-50): every channel divided by its maximum when that is
  * non-zero, then negatives clamped to 0.  hdf_normalize_petct: PETandCTNormalize (:53-68): channel 0 ->

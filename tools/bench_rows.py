@@ -7,6 +7,7 @@ bounded host-side restatement of what the reference does for the same call (nump
   python tools/bench_rows.py transforms2d                       (the full 2-D transform list row alone)
   python tools/bench_rows.py resize3d                           (the CropResize row alone)
   python tools/bench_rows.py components                         (the connected-component rows alone)
+  python tools/bench_rows.py morphology                         (the binary morphology rows alone)
   python tools/bench_rows.py slice2d                            (the slice-wise 2-D inference row alone)
 """
 import json
@@ -280,6 +281,53 @@ def components_row(shapes=((144, 144, 144), (448, 512, 512)), connectivity=26):
         torch.cuda.empty_cache()
 
 
+def morphology_row(shapes=((144, 144, 144), (448, 512, 512))):
+    """hdf_morph (dilate, 1 and 3 iterations, connectivity 6; close, 3 iterations, connectivity 18) and hdf_fill_holes
+    (connectivity 6), each timed alone with label 0 in MASK mode on the three-class blob map of components_row, next to the
+    scipy.ndimage calls on the same array, one host thread, copies not counted.  Bytes moved, hdf_morph with s steps in all:
+    the byte map read by the pack and the unpack kernel and written once (3 V), a packed buffer of P bytes written by the
+    pack kernel and read by the unpack kernel, read and written by every step (2 P + 2 s P).  hdf_fill_holes: only the
+    passes of its own kernels over the maps are counted (the complement and the flags written, the map read twice, the ids
+    read once, the output written: 9 V), not the labelling between them, whose traffic depends on the data."""
+    from hdf_rt._lib import check, lib, ptr, stream_ptr
+    from scipy import ndimage as ndi
+    import scipy
+    for shape in shapes:
+        rng = np.random.default_rng(15)
+        low = ndi.gaussian_filter(rng.random(tuple(s // 8 for s in shape)), 1.5, mode="nearest")
+        cls = np.digitize(low, np.quantile(low, [0.6, 0.8, 0.93])).astype(np.uint8)
+        vol_np = np.ascontiguousarray(cls.repeat(8, 0).repeat(8, 1).repeat(8, 2))
+        mask_np = vol_np != 0
+        vol = torch.from_numpy(vol_np).to(DEV)
+        V = vol.numel()
+        P = shape[0] * shape[1] * ((shape[2] + 31) // 32) * 4
+        ws = torch.empty(lib().hdf_morph_workspace_bytes(*shape), dtype=torch.uint8, device=DEV)
+        out = torch.empty_like(vol)
+        res = torch.empty(2, dtype=torch.int64, device=DEV)
+        st = stream_ptr()
+        rows = {}
+        for name, op, conn, n, steps, ref in (
+                ("dilate_1", 0, 6, 1, 1, lambda: ndi.binary_dilation(mask_np, ndi.generate_binary_structure(3, 1), 1)),
+                ("dilate_3", 0, 6, 3, 3, lambda: ndi.binary_dilation(mask_np, ndi.generate_binary_structure(3, 1), 3)),
+                ("close_3_c18", 3, 18, 3, 6, lambda: ndi.binary_closing(mask_np, ndi.generate_binary_structure(3, 2), 3))):
+            us = 1e3 * gpu_ms(lambda: check(lib().hdf_morph(ptr(vol), 0, op, conn, n, 0, 0, *shape, ptr(out), ptr(res), ptr(ws),
+                                                            ws.numel(), st), "hdf_morph"), reps=30, warm=5)
+            moved = 3 * V + 2 * P + 2 * steps * P
+            rows[name] = {"us": us, "bytes_moved": moved, "GBps": moved / us / 1e3, "result": res.cpu().tolist(),
+                          "scipy_s": cpu_s(ref, reps=1)}
+        del ws
+        ws = torch.empty(lib().hdf_fill_holes_workspace_bytes(*shape), dtype=torch.uint8, device=DEV)
+        us = 1e3 * gpu_ms(lambda: check(lib().hdf_fill_holes(ptr(vol), 0, 6, 0, *shape, ptr(out), ptr(res), ptr(ws), ws.numel(), st),
+                                        "hdf_fill_holes"), reps=30, warm=5)
+        rows["fill_holes_c6"] = {"us": us, "bytes_moved": 9 * V, "GBps": 9 * V / us / 1e3, "result": res.cpu().tolist(),
+                                 "scipy_s": cpu_s(lambda: ndi.binary_fill_holes(mask_np), reps=1)}
+        emit(row="morphology", config=f"{shape[0]}x{shape[1]}x{shape[2]} uint8, three classes, label 0, border_value 0, MASK mode",
+             voxels=V, packed_bytes=P, cpu_baseline={"kind": "port", "what": f"scipy {scipy.__version__} ndimage.binary_*", "threads": 1},
+             **rows)
+        del vol, ws, out
+        torch.cuda.empty_cache()
+
+
 def slice2d_row(C=3, D=24, S=384, slice_batch=24):
     """slice_predict of HDenseFormer_2D_32(3, 2, (384, 384), 24) on a 3 x 24 x 384^2 volume (the reference's 2-D workload,
     config.py:69-77; bf16, one in-plane window, no mirroring: one hdf_plane_max, one hdf_slice_gather, one forward of 24
@@ -341,6 +389,9 @@ if sys.argv[1:] == ["slice2d"]:
     sys.exit(0)
 if sys.argv[1:] == ["components"]:
     components_row()
+    sys.exit(0)
+if sys.argv[1:] == ["morphology"]:
+    morphology_row()
     sys.exit(0)
 if sys.argv[1:] == ["resize3d"]:
     resize3d_row()
