@@ -1,5 +1,5 @@
 // Process state (last error, compute-unit budget) and the one-to-one C ABI wrappers of the operator launchers: losses,
-// metrics, surface distances, connected components, binary morphology, normalisation, sliding window, augmentation, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
+// metrics, surface distances, connected components, the overlap table of two id maps, binary morphology, normalisation, sliding window, augmentation, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
 #include <atomic>
 #include <algorithm>
 #include <cstdarg>
@@ -7,6 +7,7 @@
 
 #include "../../include/hdf.h"
 #include "augment.h"
+#include "cc_pairs.h"
 #include "components.h"
 #include "conv_igemm.h"
 #include "loss.h"
@@ -309,6 +310,39 @@ int hdf_cc_filter(const uint8_t* volume, const int32_t* ids, int D, int H, int W
                 "components: filter: out overlaps volume without being volume");
   return hdf_launch_cc_filter(volume, ids, D, H, W, min_size, keep_largest, out, (unsigned long long*)result, workspace,
                               (hipStream_t)stream);
+}
+// the overlap table of two id maps (cc_pairs.hip)
+int64_t hdf_cc_pairs_workspace_bytes(int64_t capacity) {
+  if (capacity < 1 || capacity > HDF_PAIRS_MAX_CAPACITY) {
+    hdf_set_error("components: pairs: capacity %lld (1..%lld)", (long long)capacity, (long long)HDF_PAIRS_MAX_CAPACITY);
+    return -1;
+  }
+  return hdf_cc_pairs_ws_bytes(capacity);
+}
+int hdf_cc_pairs(const int32_t* ids_a, const int32_t* ids_b, const uint8_t* mask, int flags, int D, int H, int W,
+                 int64_t capacity, int64_t* pairs, uint64_t* result, void* workspace, int64_t workspace_bytes,
+                 hdf_stream stream) {
+  HDF_TRY(hdf_cc_check_dims("pairs", D, H, W));
+  HDF_CHECK_ARG(capacity >= 1 && capacity <= HDF_PAIRS_MAX_CAPACITY, "components: pairs: capacity %lld (1..%lld)",
+                (long long)capacity, (long long)HDF_PAIRS_MAX_CAPACITY);
+  HDF_CHECK_ARG((flags & ~(HDF_PAIRS_A0 | HDF_PAIRS_B0)) == 0, "components: pairs: flags %d (HDF_PAIRS_A0 | HDF_PAIRS_B0)", flags);
+  HDF_CHECK_ARG(ids_a && ids_b && pairs && result && workspace, "components: pairs: null argument");
+  const int64_t need = hdf_cc_pairs_ws_bytes(capacity), V = (int64_t)D * H * W, rows = capacity * 32;
+  HDF_CHECK_ARG(workspace_bytes >= need, "components: pairs: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+                (long long)need);
+  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "components: pairs: workspace not aligned to 8 bytes");
+  const struct { const void* p; int64_t n; const char* name; } out[3] = {{pairs, rows, "pairs"}, {result, 32, "result"},
+                                                                        {workspace, need, "workspace"}};
+  for (int i = 0; i < 3; i++) {
+    HDF_CHECK_ARG(!hdf_cc_overlap(out[i].p, out[i].n, ids_a, V * 4) && !hdf_cc_overlap(out[i].p, out[i].n, ids_b, V * 4) &&
+                      !(mask && hdf_cc_overlap(out[i].p, out[i].n, mask, V)),
+                  "components: pairs: %s overlaps an input", out[i].name);
+    for (int j = i + 1; j < 3; j++)
+      HDF_CHECK_ARG(!hdf_cc_overlap(out[i].p, out[i].n, out[j].p, out[j].n), "components: pairs: %s overlaps %s", out[i].name,
+                    out[j].name);
+  }
+  return hdf_launch_cc_pairs(ids_a, ids_b, mask, flags, D, H, W, capacity, (long long*)pairs, (unsigned long long*)result,
+                             workspace, (hipStream_t)stream);
 }
 // binary morphology (morphology.hip)
 static int morph_check_buffers(const char* who, const uint8_t* volume, const uint8_t* out, const uint64_t* result,

@@ -10,6 +10,7 @@ _COMPONENTS = ("connected_components", "component_table", "component_stats", "ke
                "remove_small_components")
 _MORPHOLOGY = ("binary_dilation", "binary_erosion", "binary_opening", "binary_closing", "binary_fill_holes", "morph_class",
                "fill_class_holes")
+_LESIONS = ("component_overlap", "match_components", "lesion_wise_scores")
 _INFERENCE = ("cal_steps", "gaussian_tables", "sliding_window_predict", "slice_predict")
 
 
@@ -30,9 +31,12 @@ def __getattr__(name):
     if name in _MORPHOLOGY:
         from . import morphology
         return getattr(morphology, name)
+    if name in _LESIONS:
+        from . import lesions
+        return getattr(lesions, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def __dir__():
     return sorted(list(globals()) + list(_AUGMENT) + list(_SURFACE) + list(_COMPONENTS) + list(_MORPHOLOGY) +
-                  list(_INFERENCE))
+                  list(_LESIONS) + list(_INFERENCE))

@@ -1,0 +1,201 @@
+"""Lesion-wise matching on the device: the overlap table of two labelings and the two per-lesion protocols built on it --
+detection matching (PI-CAI style: a predicted lesion is a hit when it overlaps a ground-truth lesion enough, its
+confidence is the peak probability inside it) and the BraTS-2023 lesion-wise Dice.  What a user does today with two copies
+of int32 id maps to the host (2 x 470 MB for a 448x512x512 volume) and np.unique over 64-bit keys on one thread.  Every
+function labels, dilates and joins on the device and makes ONE copy to the host, of a table of a few thousand words.
+Kernels: csrc/cc_pairs.hip (and components.hip, morphology.hip); definitions: include/hdf.h.  No CPU fallback.
+
+connectivity, label and the numbering of the components are those of hdf_rt.components: ids 1..n in ascending order of
+each component's smallest linear voxel index.  A [H, W] input is the depth-1 volume [1, H, W]."""
+import struct
+
+import torch
+
+from . import _lib
+from ._lib import check, lib, ptr, stream_ptr
+from .components import _label, _volume, component_table
+from .morphology import binary_dilation
+
+PAIRS_A0, PAIRS_B0 = 1, 2            # HDF_PAIRS_*
+PAIR_COLS = ("a", "b", "n", "m")
+# (device, stream, capacity) -> uint8 tensor, like components._workspaces: 256 + 24 bytes a table slot (a power of two >=
+# 2 * capacity), one per capacity and stream, never evicted -- clear_workspaces() gives the memory back
+_workspaces = {}
+
+
+def clear_workspaces():
+    _workspaces.clear()
+
+
+def _workspace(dev, capacity):
+    key = (str(dev), stream_ptr(), capacity)
+    ws = _workspaces.get(key)
+    if ws is None:
+        n = lib().hdf_cc_pairs_workspace_bytes(capacity)
+        if n < 0:
+            raise _lib.HdfError("hdf_cc_pairs_workspace_bytes: " + lib().hdf_last_error().decode(errors="replace"))
+        ws = _workspaces[key] = torch.empty(n, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _ids(t, what):
+    if not (torch.is_tensor(t) and t.dtype == torch.int32 and t.device.type == "cuda" and t.dim() in (2, 3)):
+        raise ValueError(f"{what} must be an int32 device tensor [D, H, W] or [H, W]")
+    t = t.contiguous()
+    return t[None] if t.dim() == 2 else t
+
+
+def component_overlap(ids_a, ids_b, mask=None, capacity=4096, zero_a=False, zero_b=False):
+    """(pairs int64 [capacity, 4], result int64 [4]) on the device; nothing waits on the host.  pairs: one row a, b, n, m
+    (PAIR_COLS) per distinct pair of ids that share a voxel, in ascending (a, b): n voxels, m of them where `mask` (uint8
+    or bool, same shape; None: m = 0) is non-zero; zeros behind the last pair.  Counted: a > 0 and b > 0; with zero_a also
+    a == 0 and b > 0, with zero_b also a > 0 and b == 0 -- with both, a component's size is the sum of its rows.  An id
+    below 0 counts as 0.  result: pairs, counted voxels, counted voxels under the mask, overflow (more distinct pairs than
+    `capacity`: everything else is then 0).  ids_a, ids_b: int32 device tensors, e.g. from connected_components."""
+    if not torch.cuda.is_available():
+        raise _lib.HdfError("component overlap needs a GPU (there is no CPU path)")
+    a, b = _ids(ids_a, "ids_a"), _ids(ids_b, "ids_b")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"ids_a {tuple(ids_a.shape)} and ids_b {tuple(ids_b.shape)} must match, on one device")
+    shape = tuple(int(s) for s in a.shape)
+    if mask is not None:
+        mask, _ = _volume(mask, "mask")
+        if tuple(mask.shape) != shape or mask.device != a.device:
+            raise ValueError(f"mask {tuple(mask.shape)} does not match the id maps {shape}")
+    capacity = int(capacity)
+    flags = (PAIRS_A0 if zero_a else 0) | (PAIRS_B0 if zero_b else 0)
+    with torch.cuda.device(a.device):
+        ws = _workspace(a.device, capacity)
+        pairs = torch.empty((capacity, 4), dtype=torch.int64, device=a.device)
+        res = torch.empty(4, dtype=torch.int64, device=a.device)
+        check(lib().hdf_cc_pairs(ptr(a), ptr(b), ptr(mask), flags, *shape, capacity, ptr(pairs), ptr(res), ptr(ws), ws.numel(),
+                                 stream_ptr()), "hdf_cc_pairs")
+    return pairs, res
+
+
+def _rows(host, what, capacity):
+    """the rows of a table copied to the host as a flat list: result[4], then pairs"""
+    if host[3]:
+        raise _lib.HdfError(f"{what}: more than {capacity} distinct pairs, capacity {capacity}")
+    return [host[4 + 4 * i: 8 + 4 * i] for i in range(host[0])]
+
+
+def overlap_value(n, size_a, size_b, overlap):
+    if overlap == "dice":
+        return 2.0 * n / (size_a + size_b)
+    return n / (size_a + size_b - n)          # 'iou', and the order under 'any'
+
+
+def match_components(pred, truth, connectivity=26, pred_label=0, truth_label=0, score=None, min_overlap=0.1, overlap="iou",
+                     capacity=4096):
+    """Detection matching of the components of `pred` (predicted lesions) with those of `truth`, both uint8 / bool maps:
+    label both, one overlap table with both zero flags (a component's size is the sum of its rows), with `score` (fp32,
+    non-negative, e.g. a class probability) the peak score per predicted lesion, ONE copy to the host.  The peak score is
+    hdf_cc_table's score_max: that entry fills its [capacity, 9] table as well, which is not used here.
+
+    A candidate is a pair (a, b) of a predicted and a truth lesion that share n >= 1 voxels and whose overlap is at least
+    min_overlap: 'iou' = n / (|A| + |B| - n), 'dice' = 2 n / (|A| + |B|); under 'any' every touching pair is a candidate
+    whatever min_overlap is, and its overlap is reported and ordered as the IoU.  The assignment is one-to-one and greedy in
+    descending overlap (compared as fp64 values); ties go to the smaller truth id, then to the smaller predicted id.
+
+    Returns a dict: tp, fp, fn; truth_match = per truth lesion (predicted id or 0, overlap); pred_match = per predicted
+    lesion (truth id or 0, overlap); pred_size, truth_size; confidence = the score maximum per predicted lesion, or None.
+    zip(confidence, (t > 0 for t, _ in pred_match)) are the (confidence, is_tp) records an AP / FROC aggregator takes."""
+    if overlap not in ("iou", "dice", "any"):
+        raise ValueError(f"overlap must be 'iou', 'dice' or 'any', got {overlap!r}")
+    pv, _ = _volume(pred, "pred")
+    tv, _ = _volume(truth, "truth")
+    if pv.shape != tv.shape:
+        raise ValueError(f"pred {tuple(pv.shape)} and truth {tuple(tv.shape)} must match")
+    tv = tv.to(pv.device)
+    capacity = int(capacity)
+    ids_p, res_p = _label(pv, connectivity, pred_label)
+    ids_t, res_t = _label(tv, connectivity, truth_label)
+    pairs, res = component_overlap(ids_p, ids_t, None, capacity, True, True)
+    parts = [res, pairs.reshape(-1), res_p, res_t]
+    if score is not None:
+        # (every predicted lesion has a row of the pair table: a call that does not overflow has at most `capacity` of them)
+        _, smax = component_table(pv, ids_p, score, capacity)
+        parts.append(smax.view(torch.int32).to(torch.int64))
+    host = torch.cat(parts).cpu().tolist()              # the one D2H copy
+    rows = _rows(host, "match_components", capacity)
+    tail = 4 + 4 * capacity
+    n_pred, n_truth = host[tail], host[tail + 2]
+    size_p, size_t = [0] * (n_pred + 1), [0] * (n_truth + 1)
+    for a, b, n, _m in rows:
+        size_p[a] += n
+        size_t[b] += n
+    cand = []
+    for a, b, n, _m in rows:
+        if a > 0 and b > 0:
+            ov = overlap_value(n, size_p[a], size_t[b], overlap)
+            if overlap == "any" or ov >= min_overlap:
+                cand.append((-ov, b, a))
+    cand.sort()
+    pred_match, truth_match = [(0, 0.0)] * n_pred, [(0, 0.0)] * n_truth
+    for neg, b, a in cand:
+        if pred_match[a - 1][0] == 0 and truth_match[b - 1][0] == 0:
+            pred_match[a - 1], truth_match[b - 1] = (b, -neg), (a, -neg)
+    tp = sum(1 for t, _ in pred_match if t)
+    conf = None
+    if score is not None:
+        conf = [struct.unpack("<f", struct.pack("<i", w))[0] for w in host[tail + 4: tail + 4 + n_pred]]
+    return dict(tp=tp, fp=n_pred - tp, fn=n_truth - tp, truth_match=truth_match, pred_match=pred_match, pred_size=size_p[1:],
+                truth_size=size_t[1:], confidence=conf)
+
+
+def lesion_wise_scores(pred, truth, label, dilate_iterations=3, dilate_connectivity=18, connectivity=26, min_size=0,
+                       capacity=4096):
+    """The BraTS-2023 lesion-wise Dice of class `label` (1..255).  G = truth == label; Gd = G dilated dilate_iterations
+    times under dilate_connectivity (hdf_rt.binary_dilation; 0 iterations: Gd = G); the truth lesions are the components of
+    Gd, the predicted lesions those of pred == label, both under `connectivity`.  One overlap table with mask = G and both
+    zero flags, ONE copy to the host.  For truth lesion j:
+      gt_j   = the voxels of G inside it                  P_j = the predicted lesions that share a voxel with it
+      tp_j   = the voxels of G inside it that P_j covers  dice_j = 2 tp_j / (the voxels of P_j + gt_j)
+    A truth lesion with gt_j < min_size is dropped (it neither scores nor counts).  A predicted lesion in no P_j -- of the
+    dropped lesions too -- is a false positive.  lesion_dice = sum of dice_j / (kept truth lesions + false positives), 1.0
+    when there is neither.  All in fp64.
+
+    Returns a dict: lesions = per kept truth lesion a dict (id, gt, tp, pred = the ids of P_j, pred_voxels, dice),
+    dropped = the ids of the dropped truth lesions, false_positives = the predicted ids in no P_j, fp, lesion_dice.
+    The per-lesion HD95 of the BraTS protocol is out of scope: it is not computed here."""
+    label, capacity, iters = int(label), int(capacity), int(dilate_iterations)
+    if not 1 <= label <= 255:
+        raise ValueError(f"label must be in 1..255, got {label}")
+    pv, _ = _volume(pred, "pred")
+    tv, _ = _volume(truth, "truth")
+    if pv.shape != tv.shape:
+        raise ValueError(f"pred {tuple(pv.shape)} and truth {tuple(tv.shape)} must match")
+    tv = tv.to(pv.device)
+    g = (tv == label).to(torch.uint8)
+    gd = binary_dilation(g, dilate_connectivity, iters) if iters > 0 else g
+    ids_p, res_p = _label(pv, connectivity, label)
+    ids_t, res_t = _label(gd, connectivity, 0)
+    pairs, res = component_overlap(ids_p, ids_t, g, capacity, True, True)
+    host = torch.cat([res, pairs.reshape(-1), res_p, res_t]).cpu().tolist()          # the one D2H copy
+    rows = _rows(host, "lesion_wise_scores", capacity)
+    tail = 4 + 4 * capacity
+    n_pred, n_truth = host[tail], host[tail + 2]
+    size_p = [0] * (n_pred + 1)
+    gt, tp, touching = [0] * (n_truth + 1), [0] * (n_truth + 1), [[] for _ in range(n_truth + 1)]
+    for a, b, n, m in rows:                 # ascending (a, b): every list of P_j comes out in ascending a
+        size_p[a] += n
+        gt[b] += m
+        if a > 0 and b > 0:
+            tp[b] += m
+            touching[b].append(a)
+    matched = set()
+    lesions, dropped, total = [], [], 0.0
+    for j in range(1, n_truth + 1):
+        matched.update(touching[j])
+        if gt[j] < min_size:
+            dropped.append(j)
+            continue
+        vox = sum(size_p[a] for a in touching[j])
+        dice = 2.0 * tp[j] / (vox + gt[j])
+        total += dice
+        lesions.append(dict(id=j, gt=gt[j], tp=tp[j], pred=touching[j], pred_voxels=vox, dice=dice))
+    false_pos = [a for a in range(1, n_pred + 1) if a not in matched]
+    denom = len(lesions) + len(false_pos)
+    return dict(lesions=lesions, dropped=dropped, false_positives=false_pos, fp=len(false_pos),
+                lesion_dice=total / denom if denom else 1.0)

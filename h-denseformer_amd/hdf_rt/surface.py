@@ -45,6 +45,8 @@ def clear_workspaces():
     components.clear_workspaces()      # the connected-component entries keep a cache of their own
     from . import morphology
     morphology.clear_workspaces()      # and so do the morphology entries
+    from . import lesions
+    lesions.clear_workspaces()         # and the overlap table
 
 
 def _volume(a, what):

@@ -413,6 +413,34 @@ int hdf_cc_table(const uint8_t* volume, const int32_t* ids, const float* score, 
 int hdf_cc_filter(const uint8_t* volume, const int32_t* ids, int D, int H, int W, int64_t min_size, int keep_largest,
                   uint8_t* out, uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream);
 
+/* ---- the overlap table of two id maps: which component of A meets which component of B, in how many voxels (the
+ * reference has no such code: its users copy both id maps to the host and run np.unique over 64-bit keys).  ids_a, ids_b:
+ * int32 [D][H][W] on the device, for example two outputs of hdf_cc_label; any non-negative numbering is valid, and a value
+ * below 0 counts as 0.  ids_a == ids_b is allowed: the diagonal, a component's size and masked size in one pass.
+ *   counted  a voxel with a > 0 and b > 0; with HDF_PAIRS_A0 also one with a == 0 and b > 0, with HDF_PAIRS_B0 also one
+ *            with a > 0 and b == 0.  (0, 0) is never counted.
+ *   pairs    int64 [capacity][4]: one row a, b, n, m per distinct counted (a, b), in ascending (a, b) with a major.  n = the
+ *            voxels of the pair, m = those of them with mask[v] != 0 (mask: uint8 [D][H][W], nullable -- m is then 0 in every
+ *            row).  Rows P .. capacity-1 are all zeros.
+ *   result   [4] uint64 = P, the number of distinct pairs; the counted voxels (the sum of n); the counted voxels under the
+ *            mask (the sum of m); the overflow flag, 1 iff there are more than `capacity` distinct pairs (exact: P ==
+ *            capacity is no overflow, P == capacity + 1 is one), else 0.  On overflow result[0..2] and every row of pairs are
+ *            0: no output depends on which pairs arrived first.
+ * Only integer atomics (add and compare-and-swap) are used: every output is exact and the same from call to call.  No kernel
+ * waits on another workgroup and every loop is bounded: a hash probe walks at most the table (csrc/cc_pairs.hip).  All
+ * pointers are device memory, the kernels are ordered on `stream`, nothing waits on the host, and a workspace may be reused
+ * by the next call on the same stream without clearing.  Refused (HDF_ERR_ARG, message "components: ...") before anything is
+ * launched: a dimension outside 1..1024, D*H*W >= 2^31, capacity outside 1..65536, unknown flag bits, a null required
+ * pointer, a workspace below hdf_cc_pairs_workspace_bytes(capacity) (256 + 24 bytes a slot of the table, the slots a power
+ * of two >= 2 * capacity and >= 64; -1 for a refused capacity) or not aligned to 8 bytes, pairs, result or the workspace
+ * overlapping an input or each other. */
+#define HDF_PAIRS_A0 1   /* also count voxels with a == 0, b > 0 (rows with a = 0) */
+#define HDF_PAIRS_B0 2   /* also count voxels with a > 0, b == 0 (rows with b = 0) */
+int64_t hdf_cc_pairs_workspace_bytes(int64_t capacity);
+int hdf_cc_pairs(const int32_t* ids_a, const int32_t* ids_b, const uint8_t* mask /* nullable */, int flags,
+                 int D, int H, int W, int64_t capacity, int64_t* pairs /* [capacity][4] */, uint64_t* result /* [4] */,
+                 void* workspace, int64_t workspace_bytes, hdf_stream stream);
+
 /* ---- binary morphology of a label map (the reference has no such code: its users run scipy.ndimage.binary_dilation /
  * binary_erosion / binary_opening / binary_closing / binary_fill_holes on the host).  volume: uint8 [D][H][W] on the device.
  *   input mask   label = 0: every non-zero voxel is foreground; k in 1..255: only the voxels equal to k are.

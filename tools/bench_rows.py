@@ -8,6 +8,7 @@ bounded host-side restatement of what the reference does for the same call (nump
   python tools/bench_rows.py resize3d                           (the CropResize row alone)
   python tools/bench_rows.py components                         (the connected-component rows alone)
   python tools/bench_rows.py morphology                         (the binary morphology rows alone)
+  python tools/bench_rows.py lesions                            (the lesion-wise matching rows alone)
   python tools/bench_rows.py slice2d                            (the slice-wise 2-D inference row alone)
 """
 import json
@@ -328,6 +329,80 @@ def morphology_row(shapes=((144, 144, 144), (448, 512, 512))):
         torch.cuda.empty_cache()
 
 
+def lesions_row(shapes=((144, 144, 144), (448, 512, 512))):
+    """hdf_cc_pairs (both zero flags, the truth map as the mask, 4096 rows) on the id maps hdf_cc_label gives a truth and
+    a predicted blob map -- two smoothed 1/8-resolution noise fields that share most of their noise, thresholded to a few
+    dozen lesions a map and repeated 8x along each axis -- and hdf_rt.match_components / lesion_wise_scores end to end on
+    the two maps (wall time: labelling, dilation, the table, the one copy, the host part).  Two yardsticks of the same run:
+    the host path (both id maps copied to the host, np.unique(..., return_counts=True) over the 64-bit keys, one thread),
+    and hdf_cc_table on the predicted map, a pass of the same shape.  GBps: 9 bytes a voxel over the time of the whole
+    entry (init, voxel pass, compaction, sort, rows)."""
+    from hdf_rt import lesions
+    from hdf_rt._lib import check, lib, ptr, stream_ptr
+    from hdf_rt.components import _label
+    from scipy import ndimage as ndi
+    for shape in shapes:
+        rng = np.random.default_rng(17)
+        low = tuple(s // 8 for s in shape)
+        sigma, q = (1.5, 0.93) if low[0] * low[1] * low[2] < 50000 else (3.0, 0.97)
+        f = ndi.gaussian_filter(rng.random(low), sigma, mode="nearest")
+        g = f + 0.35 * ndi.gaussian_filter(rng.random(low) - 0.5, sigma, mode="nearest")
+        up = lambda m: torch.from_numpy(np.ascontiguousarray(m.astype(np.uint8).repeat(8, 0).repeat(8, 1).repeat(8, 2))).to(DEV)
+        truth, pred = up(f > np.quantile(f, q)), up(g > np.quantile(g, q))
+        V = truth.numel()
+        ids_p, res_p = _label(pred, 26, 0)
+        ids_t, res_t = _label(truth, 26, 0)
+        cap = 4096
+        ws = torch.empty(lib().hdf_cc_pairs_workspace_bytes(cap), dtype=torch.uint8, device=DEV)
+        pairs = torch.empty((cap, 4), dtype=torch.int64, device=DEV)
+        res = torch.empty(4, dtype=torch.int64, device=DEV)
+        table = torch.empty((cap, 9), dtype=torch.int64, device=DEV)
+        st = stream_ptr()
+        us_pairs = 1e3 * gpu_ms(lambda: check(lib().hdf_cc_pairs(ptr(ids_p), ptr(ids_t), ptr(truth), 3, *shape, cap, ptr(pairs),
+                                                                 ptr(res), ptr(ws), ws.numel(), st), "hdf_cc_pairs"), reps=30, warm=5)
+        us_nomask = 1e3 * gpu_ms(lambda: check(lib().hdf_cc_pairs(ptr(ids_p), ptr(ids_t), None, 0, *shape, cap, ptr(pairs),
+                                                                  ptr(res), ptr(ws), ws.numel(), st), "hdf_cc_pairs"), reps=30, warm=5)
+        us_table = 1e3 * gpu_ms(lambda: check(lib().hdf_cc_table(ptr(pred), ptr(ids_p), None, *shape, cap, ptr(table), None, st),
+                                              "hdf_cc_table"), reps=30, warm=5)
+        check(lib().hdf_cc_pairs(ptr(ids_p), ptr(ids_t), ptr(truth), 3, *shape, cap, ptr(pairs), ptr(res), ptr(ws), ws.numel(), st),
+              "hdf_cc_pairs")
+        result = res.cpu().tolist()
+
+        def host_path():
+            a, b = ids_p.cpu().numpy().ravel().astype(np.int64), ids_t.cpu().numpy().ravel().astype(np.int64)
+            return np.unique((a << 32) | b, return_counts=True)
+
+        def wall(fn, reps):
+            fn()
+            ts = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                fn()
+                ts.append(time.perf_counter() - t)
+            return sorted(ts)[len(ts) // 2]
+
+        t = time.perf_counter()
+        keys, _ = host_path()
+        host_s = time.perf_counter() - t
+        ms_match = 1e3 * wall(lambda: lesions.match_components(pred, truth), 5)
+        ms_lw = 1e3 * wall(lambda: lesions.lesion_wise_scores(pred, truth, 1), 5)
+        lw = lesions.lesion_wise_scores(pred, truth, 1)
+        emit(row="lesions", config=f"{shape[0]}x{shape[1]}x{shape[2]}, two uint8 blob maps, connectivity 26, capacity {cap}",
+             voxels=V, pred_components=res_p.cpu().tolist()[0], truth_components=res_t.cpu().tolist()[0], pairs_result=result,
+             host_pairs=int(len(keys) - 1), hdf_cc_pairs_us=us_pairs, hdf_cc_pairs_no_mask_no_flags_us=us_nomask,
+             hdf_cc_table_us=us_table, pairs_GBps_at_9B_per_voxel=9 * V / us_pairs / 1e3,
+             no_mask_GBps_at_8B_per_voxel=8 * V / us_nomask / 1e3, match_components_ms=ms_match, lesion_wise_scores_ms=ms_lw,
+             lesion_dice=lw["lesion_dice"], lesion_false_positives=lw["fp"],
+             cpu_baseline={"kind": "port", "what": "D2H copy of both int32 id maps + np.unique(a << 32 | b, return_counts=True)",
+                           "s_per_volume": host_s, "threads": 1})
+        del truth, pred, ids_p, ids_t, ws
+        lesions.clear_workspaces()
+        from hdf_rt import surface
+        surface.clear_workspaces()
+        torch.cuda.empty_cache()
+
+
 def slice2d_row(C=3, D=24, S=384, slice_batch=24):
     """slice_predict of HDenseFormer_2D_32(3, 2, (384, 384), 24) on a 3 x 24 x 384^2 volume (the reference's 2-D workload,
     config.py:69-77; bf16, one in-plane window, no mirroring: one hdf_plane_max, one hdf_slice_gather, one forward of 24
@@ -392,6 +467,9 @@ if sys.argv[1:] == ["components"]:
     sys.exit(0)
 if sys.argv[1:] == ["morphology"]:
     morphology_row()
+    sys.exit(0)
+if sys.argv[1:] == ["lesions"]:
+    lesions_row()
     sys.exit(0)
 if sys.argv[1:] == ["resize3d"]:
     resize3d_row()
