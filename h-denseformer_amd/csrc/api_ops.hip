@@ -1,5 +1,7 @@
-// Process state (last error, compute-unit budget) and the one-to-one C ABI wrappers of the operator launchers: losses,
-// metrics, surface distances, connected components, the overlap table of two id maps, binary morphology, normalisation, sliding window, augmentation, Adam and the flat optimizer step, hdf_op_*.  Nothing here touches a plan.
+// Process state (last error, compute-unit budget) and the one-to-one C ABI wrappers of the operator launchers that work on
+// activations, logits and parameters: losses, the Dice and confusion counts, normalisation, sliding-window and slice-wise
+// inference, augmentation, Adam and the flat optimizer step, and the single operators hdf_op_*.  The entries on a label
+// volume (surface distances, components, overlap table, morphology) are in api_volume.hip.  Nothing here touches a plan.
 #include <atomic>
 #include <algorithm>
 #include <cstdarg>
@@ -7,14 +9,10 @@
 
 #include "../../include/hdf.h"
 #include "augment.h"
-#include "cc_pairs.h"
-#include "components.h"
 #include "conv_igemm.h"
 #include "loss.h"
 #include "metrics.h"
-#include "morphology.h"
 #include "optim.h"
-#include "surface.h"
 #include "transformer.h"
 #include "unet_ops.h"
 
@@ -148,248 +146,6 @@ int hdf_confusion_matrix_labels(const uint8_t* target, const uint8_t* prediction
   HDF_CHECK_ARG(target && prediction && confusion, "confusion_matrix_labels: null argument");
   return hdf_launch_confusion_labels(target, prediction, n_cls, n, (unsigned long long*)confusion, accumulate,
                                      (hipStream_t)stream);
-}
-int64_t hdf_surface_workspace_bytes(int D, int H, int W) {
-  if (hdf_surface_check_dims("workspace_bytes", D, H, W) != HDF_OK) return -1;
-  return hdf_surface_ws_bytes(D, H, W);
-}
-int hdf_op_mask_flags(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W, uint8_t* flags,
-                      uint64_t* counts, hdf_stream stream) {
-  HDF_TRY(hdf_surface_check_dims("mask_flags", D, H, W));
-  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: mask_flags: label %d (1..255)", label);
-  HDF_CHECK_ARG(target && prediction && flags && counts, "surface: mask_flags: null argument");
-  return hdf_launch_mask_flags(target, prediction, label, D, H, W, flags, (unsigned long long*)counts, false,
-                               (hipStream_t)stream);
-}
-int hdf_op_edt_sq(const uint8_t* flags, int seed_bit, int D, int H, int W, int32_t* d2, void* workspace,
-                  int64_t workspace_bytes, hdf_stream stream) {
-  HDF_TRY(hdf_surface_check_dims("edt_sq", D, H, W));
-  HDF_CHECK_ARG(seed_bit >= 1 && seed_bit <= 255, "surface: edt_sq: seed mask %d (1..255)", seed_bit);
-  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_ws_bytes(D, H, W), "surface: edt_sq: workspace of %lld bytes, %lld needed",
-                (long long)workspace_bytes, (long long)hdf_surface_ws_bytes(D, H, W));
-  HDF_CHECK_ARG(flags && d2 && workspace, "surface: edt_sq: null argument");
-  return hdf_launch_edt_sq(flags, seed_bit, D, H, W, d2, (hipStream_t)stream);
-}
-int hdf_surface_distances(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
-                          void* workspace, int64_t workspace_bytes, uint64_t* result, uint32_t* histogram_out,
-                          int64_t histogram_len, hdf_stream stream) {
-  HDF_TRY(hdf_surface_check_dims("distances", D, H, W));
-  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: distances: label %d (1..255)", label);
-  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_ws_bytes(D, H, W),
-                "surface: distances: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-                (long long)hdf_surface_ws_bytes(D, H, W));
-  HDF_CHECK_ARG(histogram_len >= 0, "surface: distances: histogram_len %lld", (long long)histogram_len);
-  HDF_CHECK_ARG(target && prediction && workspace && result, "surface: distances: null argument");
-  return hdf_launch_surface_distances(target, prediction, label, D, H, W, workspace, (unsigned long long*)result,
-                                      histogram_out, histogram_len, (hipStream_t)stream);
-}
-int64_t hdf_surface_asd_workspace_bytes(int D, int H, int W) {
-  if (hdf_surface_check_dims("asd_workspace_bytes", D, H, W) != HDF_OK) return -1;
-  return hdf_surface_asd_ws_bytes(D, H, W);
-}
-int hdf_op_edge_flags(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W, uint8_t* flags,
-                      uint64_t* counts, hdf_stream stream) {
-  HDF_TRY(hdf_surface_check_dims("edge_flags", D, H, W));
-  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: edge_flags: label %d (1..255)", label);
-  HDF_CHECK_ARG(target && prediction && flags && counts, "surface: edge_flags: null argument");
-  return hdf_launch_edge_flags(target, prediction, label, D, H, W, flags, (unsigned long long*)counts, false,
-                               (hipStream_t)stream);
-}
-int hdf_surface_asd(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W, void* workspace,
-                    int64_t workspace_bytes, uint64_t* result, uint32_t* histogram_out, int64_t histogram_len,
-                    hdf_stream stream) {
-  HDF_TRY(hdf_surface_check_dims("asd", D, H, W));
-  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: asd: label %d (1..255)", label);
-  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_asd_ws_bytes(D, H, W), "surface: asd: workspace of %lld bytes, %lld needed",
-                (long long)workspace_bytes, (long long)hdf_surface_asd_ws_bytes(D, H, W));
-  HDF_CHECK_ARG(histogram_len >= 0, "surface: asd: histogram_len %lld", (long long)histogram_len);
-  HDF_CHECK_ARG(target && prediction && workspace && result, "surface: asd: null argument");
-  return hdf_launch_surface_asd(target, prediction, label, D, H, W, workspace, (unsigned long long*)result, histogram_out,
-                                histogram_len, (hipStream_t)stream);
-}
-// the same in physical units (surface_mm.hip).  The spacing is a host pointer: checked, and read, before anything else.
-int64_t hdf_surface_mm_workspace_bytes(int D, int H, int W) {
-  if (hdf_surface_check_dims("mm_workspace_bytes", D, H, W) != HDF_OK) return -1;
-  return hdf_surface_mm_ws_bytes(D, H, W);
-}
-int hdf_op_edt_sq_mm(const uint8_t* flags, int seed_bit, int D, int H, int W, const double* spacing, double* d2,
-                     void* workspace, int64_t workspace_bytes, hdf_stream stream) {
-  SurfaceSpacing sp;
-  HDF_TRY(hdf_surface_check_spacing("edt_sq_mm", spacing, &sp));
-  HDF_TRY(hdf_surface_check_dims("edt_sq_mm", D, H, W));
-  HDF_CHECK_ARG(seed_bit >= 1 && seed_bit <= 255, "surface: edt_sq_mm: seed mask %d (1..255)", seed_bit);
-  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_mm_ws_bytes(D, H, W),
-                "surface: edt_sq_mm: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-                (long long)hdf_surface_mm_ws_bytes(D, H, W));
-  HDF_CHECK_ARG(flags && d2 && workspace, "surface: edt_sq_mm: null argument");
-  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(d2) & 7) == 0, "surface: edt_sq_mm: d2 not aligned to 8 bytes");
-  return hdf_launch_edt_sq_mm(flags, seed_bit, D, H, W, sp, d2, (hipStream_t)stream);
-}
-int hdf_op_select_u64(const uint64_t* keys, int64_t n, int64_t lo, void* workspace, int64_t workspace_bytes,
-                      uint64_t* out2, hdf_stream stream) {
-  HDF_CHECK_ARG(n >= 1 && n < ((int64_t)1 << 31), "surface: select_u64: n=%lld outside [1, 2^31)", (long long)n);
-  HDF_CHECK_ARG(lo >= 0 && lo < n, "surface: select_u64: lo=%lld outside [0, n=%lld)", (long long)lo, (long long)n);
-  HDF_CHECK_ARG(workspace_bytes >= HDF_SELECT_U64_WS, "surface: select_u64: workspace of %lld bytes, %d needed",
-                (long long)workspace_bytes, HDF_SELECT_U64_WS);
-  HDF_CHECK_ARG(keys && workspace && out2, "surface: select_u64: null argument");
-  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "surface: select_u64: workspace not aligned to 8 bytes");
-  return hdf_launch_select_u64((const unsigned long long*)keys, n, lo, workspace, (unsigned long long*)out2,
-                               (hipStream_t)stream);
-}
-int hdf_surface_distances_mm(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
-                             const double* spacing, void* workspace, int64_t workspace_bytes, uint64_t* result,
-                             hdf_stream stream) {
-  SurfaceSpacing sp;
-  HDF_TRY(hdf_surface_check_spacing("distances_mm", spacing, &sp));
-  HDF_TRY(hdf_surface_check_dims("distances_mm", D, H, W));
-  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: distances_mm: label %d (1..255)", label);
-  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_mm_ws_bytes(D, H, W),
-                "surface: distances_mm: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-                (long long)hdf_surface_mm_ws_bytes(D, H, W));
-  HDF_CHECK_ARG(target && prediction && workspace && result, "surface: distances_mm: null argument");
-  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "surface: distances_mm: workspace not aligned to 8 bytes");
-  return hdf_launch_surface_distances_mm(target, prediction, label, D, H, W, sp, workspace, (unsigned long long*)result,
-                                         (hipStream_t)stream);
-}
-int hdf_surface_asd_mm(const uint8_t* target, const uint8_t* prediction, int label, int D, int H, int W,
-                       const double* spacing, void* workspace, int64_t workspace_bytes, uint64_t* result,
-                       hdf_stream stream) {
-  SurfaceSpacing sp;
-  HDF_TRY(hdf_surface_check_spacing("asd_mm", spacing, &sp));
-  HDF_TRY(hdf_surface_check_dims("asd_mm", D, H, W));
-  HDF_CHECK_ARG(label >= 1 && label <= 255, "surface: asd_mm: label %d (1..255)", label);
-  HDF_CHECK_ARG(workspace_bytes >= hdf_surface_mm_ws_bytes(D, H, W), "surface: asd_mm: workspace of %lld bytes, %lld needed",
-                (long long)workspace_bytes, (long long)hdf_surface_mm_ws_bytes(D, H, W));
-  HDF_CHECK_ARG(target && prediction && workspace && result, "surface: asd_mm: null argument");
-  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "surface: asd_mm: workspace not aligned to 8 bytes");
-  return hdf_launch_surface_asd_mm(target, prediction, label, D, H, W, sp, workspace, (unsigned long long*)result,
-                                   (hipStream_t)stream);
-}
-// connected components (components.hip)
-int64_t hdf_cc_workspace_bytes(int D, int H, int W) {
-  if (hdf_cc_check_dims("workspace_bytes", D, H, W) != HDF_OK) return -1;
-  return hdf_cc_ws_bytes(D, H, W);
-}
-int hdf_cc_label(const uint8_t* volume, int label, int connectivity, int D, int H, int W, int32_t* ids, uint64_t* result,
-                 void* workspace, int64_t workspace_bytes, hdf_stream stream) {
-  HDF_TRY(hdf_cc_check_dims("label", D, H, W));
-  HDF_CHECK_ARG(connectivity == 6 || connectivity == 18 || connectivity == 26, "components: label: connectivity %d (6, 18 or 26)",
-                connectivity);
-  HDF_CHECK_ARG(label >= 0 && label <= 255, "components: label: label %d (0..255)", label);
-  HDF_CHECK_ARG(volume && ids && result && workspace, "components: label: null argument");
-  HDF_CHECK_ARG(workspace_bytes >= hdf_cc_ws_bytes(D, H, W), "components: label: workspace of %lld bytes, %lld needed",
-                (long long)workspace_bytes, (long long)hdf_cc_ws_bytes(D, H, W));
-  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "components: label: workspace not aligned to 8 bytes");
-  const int64_t V = (int64_t)D * H * W;
-  HDF_CHECK_ARG(!hdf_cc_overlap(volume, V, ids, V * 4), "components: label: ids overlaps volume");
-  return hdf_launch_cc_label(volume, label, connectivity, D, H, W, ids, (unsigned long long*)result, workspace,
-                             (hipStream_t)stream);
-}
-int hdf_cc_table(const uint8_t* volume, const int32_t* ids, const float* score, int D, int H, int W, int64_t capacity,
-                 int64_t* table, float* score_max, hdf_stream stream) {
-  HDF_TRY(hdf_cc_check_dims("table", D, H, W));
-  HDF_CHECK_ARG(capacity >= 1 && capacity < ((int64_t)1 << 31), "components: table: capacity %lld (1..2^31-1)",
-                (long long)capacity);
-  HDF_CHECK_ARG(volume && ids && table && (!score || score_max), "components: table: null argument");
-  const int64_t V = (int64_t)D * H * W;
-  HDF_CHECK_ARG(!hdf_cc_overlap(volume, V, ids, V * 4), "components: table: ids overlaps volume");
-  return hdf_launch_cc_table(volume, ids, score, D, H, W, capacity, (long long*)table, score_max, (hipStream_t)stream);
-}
-int hdf_cc_filter(const uint8_t* volume, const int32_t* ids, int D, int H, int W, int64_t min_size, int keep_largest,
-                  uint8_t* out, uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream) {
-  HDF_TRY(hdf_cc_check_dims("filter", D, H, W));
-  HDF_CHECK_ARG(min_size >= 0, "components: filter: min_size %lld is negative", (long long)min_size);
-  HDF_CHECK_ARG(volume && ids && out && result && workspace, "components: filter: null argument");
-  HDF_CHECK_ARG(workspace_bytes >= hdf_cc_ws_bytes(D, H, W), "components: filter: workspace of %lld bytes, %lld needed",
-                (long long)workspace_bytes, (long long)hdf_cc_ws_bytes(D, H, W));
-  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "components: filter: workspace not aligned to 8 bytes");
-  const int64_t V = (int64_t)D * H * W;
-  HDF_CHECK_ARG(!hdf_cc_overlap(volume, V, ids, V * 4) && !hdf_cc_overlap(out, V, ids, V * 4),
-                "components: filter: ids overlaps volume or out");
-  HDF_CHECK_ARG(out == volume || !hdf_cc_overlap(out, V, volume, V),
-                "components: filter: out overlaps volume without being volume");
-  return hdf_launch_cc_filter(volume, ids, D, H, W, min_size, keep_largest, out, (unsigned long long*)result, workspace,
-                              (hipStream_t)stream);
-}
-// the overlap table of two id maps (cc_pairs.hip)
-int64_t hdf_cc_pairs_workspace_bytes(int64_t capacity) {
-  if (capacity < 1 || capacity > HDF_PAIRS_MAX_CAPACITY) {
-    hdf_set_error("components: pairs: capacity %lld (1..%lld)", (long long)capacity, (long long)HDF_PAIRS_MAX_CAPACITY);
-    return -1;
-  }
-  return hdf_cc_pairs_ws_bytes(capacity);
-}
-int hdf_cc_pairs(const int32_t* ids_a, const int32_t* ids_b, const uint8_t* mask, int flags, int D, int H, int W,
-                 int64_t capacity, int64_t* pairs, uint64_t* result, void* workspace, int64_t workspace_bytes,
-                 hdf_stream stream) {
-  HDF_TRY(hdf_cc_check_dims("pairs", D, H, W));
-  HDF_CHECK_ARG(capacity >= 1 && capacity <= HDF_PAIRS_MAX_CAPACITY, "components: pairs: capacity %lld (1..%lld)",
-                (long long)capacity, (long long)HDF_PAIRS_MAX_CAPACITY);
-  HDF_CHECK_ARG((flags & ~(HDF_PAIRS_A0 | HDF_PAIRS_B0)) == 0, "components: pairs: flags %d (HDF_PAIRS_A0 | HDF_PAIRS_B0)", flags);
-  HDF_CHECK_ARG(ids_a && ids_b && pairs && result && workspace, "components: pairs: null argument");
-  const int64_t need = hdf_cc_pairs_ws_bytes(capacity), V = (int64_t)D * H * W, rows = capacity * 32;
-  HDF_CHECK_ARG(workspace_bytes >= need, "components: pairs: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-                (long long)need);
-  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "components: pairs: workspace not aligned to 8 bytes");
-  const struct { const void* p; int64_t n; const char* name; } out[3] = {{pairs, rows, "pairs"}, {result, 32, "result"},
-                                                                        {workspace, need, "workspace"}};
-  for (int i = 0; i < 3; i++) {
-    HDF_CHECK_ARG(!hdf_cc_overlap(out[i].p, out[i].n, ids_a, V * 4) && !hdf_cc_overlap(out[i].p, out[i].n, ids_b, V * 4) &&
-                      !(mask && hdf_cc_overlap(out[i].p, out[i].n, mask, V)),
-                  "components: pairs: %s overlaps an input", out[i].name);
-    for (int j = i + 1; j < 3; j++)
-      HDF_CHECK_ARG(!hdf_cc_overlap(out[i].p, out[i].n, out[j].p, out[j].n), "components: pairs: %s overlaps %s", out[i].name,
-                    out[j].name);
-  }
-  return hdf_launch_cc_pairs(ids_a, ids_b, mask, flags, D, H, W, capacity, (long long*)pairs, (unsigned long long*)result,
-                             workspace, (hipStream_t)stream);
-}
-// binary morphology (morphology.hip)
-static int morph_check_buffers(const char* who, const uint8_t* volume, const uint8_t* out, const uint64_t* result,
-                               const void* workspace, int64_t workspace_bytes, int64_t need, int64_t V) {
-  HDF_CHECK_ARG(volume && out && result && workspace, "morphology: %s: null argument", who);
-  HDF_CHECK_ARG(workspace_bytes >= need, "morphology: %s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes,
-                (long long)need);
-  HDF_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "morphology: %s: workspace not aligned to 8 bytes", who);
-  HDF_CHECK_ARG(out == volume || !hdf_cc_overlap(out, V, volume, V), "morphology: %s: out overlaps volume without being volume",
-                who);
-  HDF_CHECK_ARG(!hdf_cc_overlap(workspace, need, volume, V) && !hdf_cc_overlap(workspace, need, out, V) &&
-                    !hdf_cc_overlap(workspace, need, result, 16),
-                "morphology: %s: workspace overlaps volume, out or result", who);
-  HDF_CHECK_ARG(!hdf_cc_overlap(result, 16, volume, V) && !hdf_cc_overlap(result, 16, out, V),
-                "morphology: %s: result overlaps volume or out", who);
-  return HDF_OK;
-}
-int64_t hdf_morph_workspace_bytes(int D, int H, int W) {
-  if (hdf_morph_check_dims("workspace_bytes", D, H, W) != HDF_OK) return -1;
-  return hdf_morph_ws_bytes(D, H, W);
-}
-int hdf_morph(const uint8_t* volume, int label, int op, int connectivity, int iterations, int border_value, int mode, int D,
-              int H, int W, uint8_t* out, uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream) {
-  HDF_TRY(hdf_morph_check_dims("morph", D, H, W));
-  HDF_CHECK_ARG(op == HDF_MORPH_DILATE || op == HDF_MORPH_ERODE || op == HDF_MORPH_OPEN || op == HDF_MORPH_CLOSE,
-                "morphology: morph: op %d (HDF_MORPH_DILATE, _ERODE, _OPEN or _CLOSE)", op);
-  HDF_TRY(hdf_morph_check_mask_args("morph", label, connectivity, mode));
-  HDF_CHECK_ARG(iterations >= 1 && iterations <= HDF_MORPH_MAX_ITER, "morphology: morph: iterations %d (1..%d)", iterations,
-                HDF_MORPH_MAX_ITER);
-  HDF_CHECK_ARG(border_value == 0 || border_value == 1, "morphology: morph: border_value %d (0 or 1)", border_value);
-  HDF_TRY(morph_check_buffers("morph", volume, out, result, workspace, workspace_bytes, hdf_morph_ws_bytes(D, H, W),
-                              (int64_t)D * H * W));
-  return hdf_launch_morph(volume, label, op, connectivity, iterations, border_value, mode, D, H, W, out,
-                          (unsigned long long*)result, workspace, (hipStream_t)stream);
-}
-int64_t hdf_fill_holes_workspace_bytes(int D, int H, int W) {
-  if (hdf_morph_check_dims("workspace_bytes", D, H, W) != HDF_OK) return -1;
-  return hdf_fill_holes_ws_bytes(D, H, W);
-}
-int hdf_fill_holes(const uint8_t* volume, int label, int connectivity, int mode, int D, int H, int W, uint8_t* out,
-                   uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream) {
-  HDF_TRY(hdf_morph_check_dims("fill_holes", D, H, W));
-  HDF_TRY(hdf_morph_check_mask_args("fill_holes", label, connectivity, mode));
-  HDF_TRY(morph_check_buffers("fill_holes", volume, out, result, workspace, workspace_bytes, hdf_fill_holes_ws_bytes(D, H, W),
-                              (int64_t)D * H * W));
-  return hdf_launch_fill_holes(volume, label, connectivity, mode, D, H, W, out, (unsigned long long*)result, workspace,
-                               (hipStream_t)stream);
 }
 int64_t hdf_normalize_workspace_bytes(int channels) { return (int64_t)hdf_norm_ws_bytes(channels); }
 int hdf_normalize_mr(float* image, int channels, int64_t voxels, void* workspace, hdf_stream stream) {

@@ -50,11 +50,6 @@ __device__ __forceinline__ u64 ld64(const u64* p) { return __hip_atomic_load(p, 
 __device__ __forceinline__ uint32_t ld32(const uint32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ uint32_t hash_key(u64 k) {
   k ^= k >> 33;
   k *= 0xff51afd7ed558ccdull;
@@ -132,8 +127,7 @@ __global__ __launch_bounds__(256) void pairs_voxel_kernel(const int32_t* __restr
       const bool head = counted && (lane == 0 || pa != a || pb != b || x == 0);
       const u64 brk = __ballot(head || !counted), under = __ballot(counted && vm[k] != 0);
       if (head) {
-        const u64 above = lane == 63 ? 0ull : brk >> (lane + 1);
-        const int len = above ? __ffsll((long long)above) : 64 - lane;
+        const int len = wave_run_len(brk, lane);
         const u64 run = (len == 64 ? ~0ull : (1ull << len) - 1) << lane;
         const uint32_t m = (uint32_t)__popcll(under & run);
         const u64 key = ((u64)(uint32_t)a << 32) | (uint32_t)b;

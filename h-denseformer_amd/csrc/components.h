@@ -3,14 +3,12 @@
 #pragma once
 #include "../../include/hdf.h"
 #include "hdf_common.h"
+#include "volume_host.h"
 
 constexpr int HDF_CC_MAX_DIM = 1024;
+static_assert(HDF_CC_MAX_DIM == HDF_VOL_MAX_DIM, "hdf_vol_check_dims: one cap");
 constexpr int HDF_CC_TABLE_COLS = 9;   // size value first zmin zmax ymin ymax xmin xmax
 
-// host-side argument checks shared by the entries: HDF_ERR_ARG with a "components:" message
-int hdf_cc_check_dims(const char* who, int D, int H, int W);
-// [a, a + na) and [b, b + nb) share a byte
-bool hdf_cc_overlap(const void* a, int64_t na, const void* b, int64_t nb);
 int64_t hdf_cc_ws_bytes(int D, int H, int W);
 
 int hdf_launch_cc_label(const uint8_t* vol, int label, int connectivity, int D, int H, int W, int32_t* ids,

@@ -57,25 +57,6 @@ __device__ __forceinline__ int unite(int32_t* L, int a, int b) {
   return a;
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
-    v = max(v, ((unsigned long long)hi << 32) | lo);
-  }
-  return v;
-}
-
 // ------------------------------------------------------------------------------------------------ label
 __global__ __launch_bounds__(256) void cc_init_kernel(const uint8_t* __restrict__ vol, int label, int64_t V,
                                                       int32_t* __restrict__ L) {
@@ -189,12 +170,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void cc_scan_kernel(uint32_t* __restr
     const int64_t b = b0 + threadIdx.x;
     const uint32_t c = b < nblk ? blk[2 * b] : 0;
     fg += b < nblk ? blk[2 * b + 1] : 0;
-    uint32_t inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += up;
-    }
+    const uint32_t inc = wave_scan_incl_u32(c, lane);
     if (lane == 63) wtot[par][wave] = inc;
     __syncthreads();   // (the other parity's slots are rewritten only after the next trip's barrier)
     uint32_t off = carry + (inc - c), total = 0;
@@ -227,12 +203,7 @@ __global__ __launch_bounds__(256) void cc_rank_kernel(int32_t* __restrict__ L, i
     root[k] = v0 + k < V && L[v0 + k] == (int)(v0 + k);
     c += root[k];
   }
-  uint32_t inc = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t up = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += up;
-  }
+  const uint32_t inc = wave_scan_incl_u32(c, lane);
   if (lane == 63) wtot[wave] = inc;
   __syncthreads();
   uint32_t rank = blk[2 * (int64_t)blockIdx.x] + (inc - c);   // roots before this thread's first voxel
@@ -258,9 +229,7 @@ __device__ __forceinline__ int wave_run(int id, bool row_start, bool* head) {
   const int lane = threadIdx.x & 63;
   const int prev = __shfl_up(id, 1, 64);
   *head = id > 0 && (lane == 0 || prev != id || row_start);
-  const unsigned long long brk = __ballot(*head || id <= 0);
-  const unsigned long long above = lane == 63 ? 0ull : brk >> (lane + 1);
-  return above ? __ffsll((long long)above) : 64 - lane;
+  return wave_run_len(__ballot(*head || id <= 0), lane);
 }
 
 // ------------------------------------------------------------------------------------------------ table
@@ -454,6 +423,7 @@ __global__ __launch_bounds__(256) void cc_select_kernel(const uint32_t* __restri
     }
   }
   if (keep_largest) return;
+  // (written out, not block_add_counts: behind the early return the shared form compiles to one instruction more)
   cnt = wave_sum_u32(cnt);
   if (lane == 0) wsum[threadIdx.x >> 6] = cnt;
   __syncthreads();
@@ -468,7 +438,6 @@ __global__ __launch_bounds__(256) void cc_keep_kernel(const uint8_t* vol, const 
                                                       const uint32_t* __restrict__ sizes,
                                                       const unsigned long long* __restrict__ best, long long min_size,
                                                       int keep_largest, uint8_t* out, FilterScalars* __restrict__ sc) {
-  __shared__ uint32_t wsum[4];
   uint32_t cnt = 0;
   for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (int64_t)gridDim.x * 256) {
     const int id = ids[v];
@@ -481,13 +450,7 @@ __global__ __launch_bounds__(256) void cc_keep_kernel(const uint8_t* vol, const 
     out[v] = keep ? val : (uint8_t)0;
     cnt += keep;
   }
-  cnt = wave_sum_u32(cnt);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long t = (unsigned long long)wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    if (t) atomicAdd(&sc->voxels, t);
-  }
+  block_add_counts({cnt}, &sc->voxels);
 }
 
 // one workgroup of 256: thread t looks at value t
@@ -511,33 +474,18 @@ struct Carve {
   int64_t scalars, best, words, bytes, blk, total, nblk;
   Carve(int D, int H, int W) {
     const int64_t V = (int64_t)D * H * W;
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
+    Carver c;
     nblk = ceil_div64(V, CHUNK);
-    scalars = 0;
-    best = 256;                      // 256 uint64
-    words = best + 2048;             // label: the parent map; filter: the size of every component (there are at most V)
-    bytes = words + up(V * 4);       // filter: the value of every component
-    blk = bytes + up(V);             // label: two uint32 per block of CHUNK voxels
-    total = blk + up(nblk * 8);
+    scalars = c.take(256);
+    best = c.take(2048);         // 256 uint64
+    words = c.take(V * 4);       // label: the parent map; filter: the size of every component (there are at most V)
+    bytes = c.take(V);           // filter: the value of every component
+    blk = c.take(nblk * 8);      // label: two uint32 per block of CHUNK voxels
+    total = c.at;
   }
 };
-
-unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div64(n, 256), 1), 1 << 22); }
 }  // namespace
 
-int hdf_cc_check_dims(const char* who, int D, int H, int W) {
-  const int M = HDF_CC_MAX_DIM;
-  HDF_CHECK_ARG(D >= 1 && D <= M && H >= 1 && H <= M && W >= 1 && W <= M, "components: %s: volume %dx%dx%d (each of 1..%d)",
-                who, D, H, W, M);
-  // (with every dimension at most 1024 the product is at most 2^30; the kernels' 32-bit voxel indices rest on this bound,
-  // so it is stated where the cap could one day be raised)
-  HDF_CHECK_ARG((int64_t)D * H * W < (1ll << 31), "components: %s: %dx%dx%d has 2^31 voxels or more", who, D, H, W);
-  return HDF_OK;
-}
-bool hdf_cc_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
-}
 int64_t hdf_cc_ws_bytes(int D, int H, int W) { return Carve(D, H, W).total; }
 
 int hdf_launch_cc_label(const uint8_t* vol, int label, int connectivity, int D, int H, int W, int32_t* ids,
@@ -546,7 +494,7 @@ int hdf_launch_cc_label(const uint8_t* vol, int label, int connectivity, int D, 
   const int64_t V = (int64_t)D * H * W;
   int32_t* L = (int32_t*)((char*)ws + cv.words);
   uint32_t* blk = (uint32_t*)((char*)ws + cv.blk);
-  const unsigned gv = grid_for(V), gb = (unsigned)cv.nblk;
+  const unsigned gv = vol_grid(V, 1 << 22), gb = (unsigned)cv.nblk;
   hipLaunchKernelGGL(cc_init_kernel, dim3(gv), dim3(256), 0, stream, vol, label, V, L);
   HDF_LAUNCH_CHECK();
   if (connectivity == 6)
@@ -570,7 +518,7 @@ int hdf_launch_cc_label(const uint8_t* vol, int label, int connectivity, int D, 
 int hdf_launch_cc_table(const uint8_t* vol, const int32_t* ids, const float* score, int D, int H, int W, int64_t capacity,
                         long long* table, float* score_max, hipStream_t stream) {
   const int64_t V = (int64_t)D * H * W;
-  const unsigned gc = (unsigned)std::min<int64_t>(grid_for(capacity * HDF_CC_TABLE_COLS), 4096);
+  const unsigned gc = vol_grid(capacity * HDF_CC_TABLE_COLS, 4096);
   hipLaunchKernelGGL(cc_table_init_kernel, dim3(gc), dim3(256), 0, stream, table, capacity, score ? score_max : nullptr);
   HDF_LAUNCH_CHECK();
   hipLaunchKernelGGL(cc_table_kernel, dim3((unsigned)ceil_div64(V, SPAN)), dim3(256), 0, stream, vol, ids, score, H, W, V,
@@ -592,18 +540,15 @@ int hdf_launch_cc_filter(const uint8_t* vol, const int32_t* ids, int D, int H, i
   uint32_t* sizes = (uint32_t*)(w + cv.words);
   uint8_t* value = (uint8_t*)(w + cv.bytes);
   // the scalars, the per-value maxima and the sizes of an earlier call are cleared on the stream, ahead of the kernels
-  if (hipMemsetAsync(w, 0, (size_t)(cv.words + V * 4), stream) != hipSuccess) {
-    hdf_set_error("components: memset failed");
-    return HDF_ERR_HIP;
-  }
+  HDF_TRY(hdf_zero_async("components", w, (size_t)(cv.words + V * 4), stream));
   hipLaunchKernelGGL(cc_size_kernel, dim3((unsigned)ceil_div64(V, SPAN)), dim3(256), 0, stream, vol, ids, V, sizes, value, sc);
   HDF_LAUNCH_CHECK();
-  const unsigned gs = std::min(grid_for(V), 4096u);   // over the components, whose number only the device knows
+  const unsigned gs = vol_grid(V, 4096);   // over the components, whose number only the device knows
   hipLaunchKernelGGL(cc_select_kernel, dim3(gs), dim3(256), 0, stream, (const uint32_t*)sizes, (const uint8_t*)value,
                      (long long)min_size, keep_largest, best, sc);
   HDF_LAUNCH_CHECK();
   // (every workgroup ends with one atomic on the same counter: a few thousand of them, not one per 256 voxels)
-  hipLaunchKernelGGL(cc_keep_kernel, dim3(std::min(grid_for(V), 4096u)), dim3(256), 0, stream, vol, ids, V, (const uint32_t*)sizes,
+  hipLaunchKernelGGL(cc_keep_kernel, dim3(gs), dim3(256), 0, stream, vol, ids, V, (const uint32_t*)sizes,
                      (const unsigned long long*)best, (long long)min_size, keep_largest, out, sc);
   HDF_LAUNCH_CHECK();
   hipLaunchKernelGGL(cc_filter_result_kernel, dim3(1), dim3(256), 0, stream, (const unsigned long long*)best,

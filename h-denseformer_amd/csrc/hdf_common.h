@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "wave_ops.h"
+
 #define HDF_OK 0
 #define HDF_ERR_ARG 1
 #define HDF_ERR_HIP 2
@@ -223,18 +225,7 @@ __host__ __device__ __forceinline__ uint32_t hdf_site_id(int m, int b, int l, in
   return (uint32_t)(((m * 64 + b) * 8 + l) * 8 + kind);
 }
 
-// ---------------------------------------------------------------------------------------------
-// wave helpers (wave = 64 lanes)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
+// wave helpers (wave = 64 lanes): wave_ops.h, included above
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }

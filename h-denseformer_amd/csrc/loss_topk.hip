@@ -145,12 +145,6 @@ __global__ __launch_bounds__(256) void topk_pick_kernel(const uint32_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ rank and compaction
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // block b owns the indices [b * chunk, min(n, (b + 1) * chunk)): output order is index order
 __global__ __launch_bounds__(256) void topk_count_kernel(const float* __restrict__ values, int64_t n, int64_t chunk,
                                                          const TopkState* __restrict__ state,

@@ -3,12 +3,13 @@
 #pragma once
 #include "../../include/hdf.h"
 #include "hdf_common.h"
+#include "volume_host.h"
 
 constexpr int HDF_MORPH_MAX_DIM = 1024;
+static_assert(HDF_MORPH_MAX_DIM == HDF_VOL_MAX_DIM, "hdf_vol_check_dims: one cap");
 constexpr int HDF_MORPH_MAX_ITER = 256;
 
-// host-side argument checks shared by the entries: HDF_ERR_ARG with a "morphology:" message
-int hdf_morph_check_dims(const char* who, int D, int H, int W);
+// host-side argument check shared by the entries: HDF_ERR_ARG with a "morphology:" message
 int hdf_morph_check_mask_args(const char* who, int label, int connectivity, int mode);
 int64_t hdf_morph_ws_bytes(int D, int H, int W);
 int64_t hdf_fill_holes_ws_bytes(int D, int H, int W);

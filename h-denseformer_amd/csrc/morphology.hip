@@ -28,12 +28,6 @@ struct Bytes16 {
   };
 };
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ bool in_mask(int val, int label) { return label ? val == label : val != 0; }
 
 // n of the 16 voxels at p exist (the others read as 0, which is in no mask)
@@ -50,19 +44,6 @@ __device__ __forceinline__ uint32_t mask_bits(const Bytes16& d, int label) {
 #pragma unroll
   for (int k = 0; k < LANE_VOX; k++) bits |= (uint32_t)in_mask(d.b[k], label) << k;
   return bits;
-}
-
-// both result words from the per-thread counts: one pair of integer atomics a workgroup
-__device__ __forceinline__ void add_result(uint32_t cnt, uint32_t chg, unsigned long long* __restrict__ result) {
-  __shared__ uint32_t wsum[4][2];
-  cnt = wave_sum_u32(cnt), chg = wave_sum_u32(chg);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][0] = cnt, wsum[threadIdx.x >> 6][1] = chg;
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const unsigned long long t =
-        (unsigned long long)wsum[0][threadIdx.x] + wsum[1][threadIdx.x] + wsum[2][threadIdx.x] + wsum[3][threadIdx.x];
-    if (t) atomicAdd(result + threadIdx.x, t);
-  }
 }
 
 // ------------------------------------------------------------------------------------------------ pack
@@ -167,7 +148,7 @@ __global__ __launch_bounds__(256) void morph_unpack_kernel(const uint32_t* __res
         if (k < n) out[at + k] = o.b[k];
     }
   }
-  add_result(cnt, chg, result);
+  block_add_counts({cnt, chg}, result);   // one pair of integer atomics a workgroup
 }
 
 // ------------------------------------------------------------------------------------------------ fill holes
@@ -220,10 +201,9 @@ __global__ __launch_bounds__(256) void fill_write_kernel(const uint8_t* vol, con
     else
       out[v] = was || hole;
   }
-  add_result(cnt, chg, result);
+  block_add_counts({cnt, chg}, result);
 }
 
-int64_t up256(int64_t b) { return (b + 255) / 256 * 256; }
 int words_per_row(int W) { return (W + 31) / 32; }
 int64_t packed_bytes(int D, int H, int W) { return up256((int64_t)D * H * words_per_row(W) * 4); }
 
@@ -232,26 +212,17 @@ struct FillCarve {
   int64_t scalars, comp, ids, flag, cc, total;
   FillCarve(int D, int H, int W) {
     const int64_t V = (int64_t)D * H * W;
-    scalars = 0;                     // result[2] of the labelling
-    comp = 256;                      // the complement map, uint8
-    ids = comp + up256(V);           // its component ids, int32
-    flag = ids + up256(V * 4);       // a byte per id 0 .. V
-    cc = flag + up256(V + 1);        // the labelling's own workspace
-    total = cc + up256(hdf_cc_ws_bytes(D, H, W));
+    Carver c;
+    scalars = c.take(256);                      // result[2] of the labelling
+    comp = c.take(V);                           // the complement map, uint8
+    ids = c.take(V * 4);                        // its component ids, int32
+    flag = c.take(V + 1);                       // a byte per id 0 .. V
+    cc = c.take(hdf_cc_ws_bytes(D, H, W));      // the labelling's own workspace
+    total = c.at;
   }
 };
 
-unsigned grid_for(int64_t n, int64_t cap) { return (unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div64(n, 256), 1), cap); }
-
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int clear_result(unsigned long long* result, hipStream_t stream) {
-  if (hipMemsetAsync(result, 0, 16, stream) != hipSuccess) {
-    hdf_set_error("morphology: memset failed");
-    return HDF_ERR_HIP;
-  }
-  return HDF_OK;
-}
 
 template <bool ERODE>
 void launch_step(int c, unsigned grid, hipStream_t stream, const uint32_t* src, uint32_t* dst, int D, int H, int wpr, uint32_t tail,
@@ -265,14 +236,6 @@ void launch_step(int c, unsigned grid, hipStream_t stream, const uint32_t* src, 
 }
 }  // namespace
 
-int hdf_morph_check_dims(const char* who, int D, int H, int W) {
-  const int M = HDF_MORPH_MAX_DIM;
-  HDF_CHECK_ARG(D >= 1 && D <= M && H >= 1 && H <= M && W >= 1 && W <= M, "morphology: %s: volume %dx%dx%d (each of 1..%d)",
-                who, D, H, W, M);
-  // (at most 2^30 with the cap above; the kernels' 32-bit word and lane indices rest on this bound)
-  HDF_CHECK_ARG((int64_t)D * H * W < (1ll << 31), "morphology: %s: %dx%dx%d has 2^31 voxels or more", who, D, H, W);
-  return HDF_OK;
-}
 int hdf_morph_check_mask_args(const char* who, int label, int connectivity, int mode) {
   HDF_CHECK_ARG(connectivity == 6 || connectivity == 18 || connectivity == 26, "morphology: %s: connectivity %d (6, 18 or 26)",
                 who, connectivity);
@@ -292,12 +255,12 @@ int hdf_launch_morph(const uint8_t* vol, int label, int op, int connectivity, in
   const uint32_t tail = W % 32 ? (1u << (W % 32)) - 1u : ~0u, fill = border_value ? ~0u : 0u;
   const bool vec = W % LANE_VOX == 0 && aligned16(vol) && aligned16(out);
   uint32_t* buf[2] = {(uint32_t*)ws, (uint32_t*)((char*)ws + packed_bytes(D, H, W))};
-  hipLaunchKernelGGL(morph_pack_kernel, dim3(grid_for(lanes, 1 << 22)), dim3(256), 0, stream, vol, label, W, wpr, lanes, vec,
+  hipLaunchKernelGGL(morph_pack_kernel, dim3(vol_grid(lanes, 1 << 22)), dim3(256), 0, stream, vol, label, W, wpr, lanes, vec,
                      buf[0]);
   HDF_LAUNCH_CHECK();
   const bool erode_first = op == HDF_MORPH_ERODE || op == HDF_MORPH_OPEN;
   const int halves = op == HDF_MORPH_OPEN || op == HDF_MORPH_CLOSE ? 2 : 1;
-  const unsigned gs = grid_for(words, 1 << 22);
+  const unsigned gs = vol_grid(words, 1 << 22);
   int cur = 0;
   for (int half = 0; half < halves; half++) {
     const bool erode = erode_first != (half == 1);
@@ -309,9 +272,9 @@ int hdf_launch_morph(const uint8_t* vol, int label, int op, int connectivity, in
       HDF_LAUNCH_CHECK();
     }
   }
-  HDF_TRY(clear_result(result, stream));
+  HDF_TRY(hdf_zero_async("morphology", result, 16, stream));
   // (every workgroup ends with one atomic a result word: a few thousand of them)
-  const unsigned gu = grid_for(lanes, 4096);
+  const unsigned gu = vol_grid(lanes, 4096);
   if (mode == HDF_MORPH_MAP)
     hipLaunchKernelGGL(morph_unpack_kernel<true>, dim3(gu), dim3(256), 0, stream, (const uint32_t*)buf[cur], vol, label, W, wpr,
                        lanes, vec, out, result);
@@ -330,16 +293,16 @@ int hdf_launch_fill_holes(const uint8_t* vol, int label, int connectivity, int m
   uint8_t* comp = (uint8_t*)(w + cv.comp);
   int32_t* ids = (int32_t*)(w + cv.ids);
   uint8_t* flag = (uint8_t*)(w + cv.flag);
-  const unsigned gv = grid_for(V, 1 << 22);
+  const unsigned gv = vol_grid(V, 1 << 22);
   hipLaunchKernelGGL(fill_complement_kernel, dim3(gv), dim3(256), 0, stream, vol, label, V, comp, flag);
   HDF_LAUNCH_CHECK();
   HDF_TRY(hdf_launch_cc_label(comp, 1, connectivity, D, H, W, ids, (unsigned long long*)(w + cv.scalars), w + cv.cc, stream));
   const int64_t nz = D > 1 ? (int64_t)H * W : 0, ny = (int64_t)D * W, nx = (int64_t)D * H;   // a depth-1 volume has no z face
-  hipLaunchKernelGGL(fill_faces_kernel, dim3(grid_for(2 * (nz + ny + nx), 1 << 22)), dim3(256), 0, stream, (const int32_t*)ids, D,
+  hipLaunchKernelGGL(fill_faces_kernel, dim3(vol_grid(2 * (nz + ny + nx), 1 << 22)), dim3(256), 0, stream, (const int32_t*)ids, D,
                      H, W, nz, ny, nx, V, flag);
   HDF_LAUNCH_CHECK();
-  HDF_TRY(clear_result(result, stream));
-  const unsigned gw = grid_for(V, 4096);
+  HDF_TRY(hdf_zero_async("morphology", result, 16, stream));
+  const unsigned gw = vol_grid(V, 4096);
   if (mode == HDF_MORPH_MAP)
     hipLaunchKernelGGL(fill_write_kernel<true>, dim3(gw), dim3(256), 0, stream, vol, (const int32_t*)ids, (const uint8_t*)flag, label,
                        V, out, result);

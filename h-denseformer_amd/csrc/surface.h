@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/hdf.h"  // HDF_EDT_NO_SEED
 #include "hdf_common.h"
+#include "volume_host.h"
 
 // flag byte of one voxel (hdf_op_mask_flags)
 enum {
@@ -20,9 +21,8 @@ enum {
 // "no seed anywhere" is HDF_EDT_NO_SEED (include/hdf.h): + 1023^2 = 1 074 788 352 < 2^31, and every real squared
 // distance (at most 3 * 1023^2) is below it
 constexpr int HDF_SURFACE_MAX_DIM = 1024;
+static_assert(HDF_SURFACE_MAX_DIM == HDF_VOL_MAX_DIM, "hdf_vol_check_dims: one cap");
 
-// host-side argument check shared by the entries: HDF_ERR_ARG with a "surface:" message
-int hdf_surface_check_dims(const char* who, int D, int H, int W);
 int64_t hdf_surface_ws_bytes(int D, int H, int W);
 // bins of the squared-distance histogram: (D-1)^2 + (H-1)^2 + (W-1)^2 + 1
 int64_t hdf_surface_hist_bins(int D, int H, int W);
@@ -45,6 +45,9 @@ int hdf_launch_edge_flags(const uint8_t* tgt, const uint8_t* pred, int label, in
                           unsigned long long* counts, bool counts_are_zero, hipStream_t st);
 int hdf_launch_surface_asd(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, void* ws,
                            unsigned long long* result, uint32_t* hist_out, int64_t hist_len, hipStream_t st);
+// asd_final_kernel, one workgroup: result[4] from counts[2] and the 2 x nblk partial sums (also what surface_mm.hip ends with)
+int hdf_launch_asd_final(const unsigned long long* counts, const double* partial, uint32_t nblk, unsigned long long* result,
+                         hipStream_t st);
 
 // the same measures in physical units (surface_mm.hip): squared distances are fp64, weighted per axis by the squared spacing
 struct SurfaceSpacing {

@@ -16,24 +16,12 @@
 namespace {
 constexpr int32_t SENT = HDF_EDT_NO_SEED;
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o, 64));
-  return v;
-}
-
 // ------------------------------------------------------------------------------------------------ mask flags
 // A voxel outside both masks (most of a volume) costs two byte loads; one inside a mask reads its in-volume neighbours.
 // Neighbours outside the volume do not exist: they never make a voxel a border voxel.
 __global__ __launch_bounds__(256) void mask_flags_kernel(const uint8_t* __restrict__ tgt, const uint8_t* __restrict__ pred,
                                                          int label, int D, int H, int W, uint8_t* __restrict__ flags,
                                                          unsigned long long* __restrict__ counts) {
-  __shared__ uint32_t red[4][5];
   const int64_t V = (int64_t)D * H * W;
   const uint32_t HW = (uint32_t)H * W;
   uint32_t cnt[5] = {0, 0, 0, 0, 0};   // nT nP nI |C6(T)| |C6(P)|: a thread sees fewer than 2^31 voxels
@@ -67,19 +55,7 @@ __global__ __launch_bounds__(256) void mask_flags_kernel(const uint8_t* __restri
     cnt[0] += inT, cnt[1] += inP, cnt[2] += (inT && inP);
     cnt[3] += (f & HDF_SF_C6_T) != 0, cnt[4] += (f & HDF_SF_C6_P) != 0;
   }
-  // per wave, per block, then one atomic per block and count
-#pragma unroll
-  for (int k = 0; k < 5; k++) cnt[k] = wave_sum_u32(cnt[k]);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; k++) red[threadIdx.x >> 6][k] = cnt[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    const unsigned long long s = (unsigned long long)red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] +
-                                 red[3][threadIdx.x];
-    if (s) atomicAdd(counts + threadIdx.x, s);
-  }
+  block_add_counts(cnt, counts);
 }
 
 // ------------------------------------------------------------------------------------------------ exact squared EDT
@@ -254,12 +230,7 @@ __global__ __launch_bounds__(SEL_THREADS) void surface_select_kernel(const unsig
 #pragma unroll
     for (int k = 0; k < 4; k++) h[k] = b + k < nbins ? hist[b + k] : 0;
     const uint32_t mine = h[0] + h[1] + h[2] + h[3];
-    uint32_t inc = mine;   // inclusive scan over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += up;
-    }
+    const uint32_t inc = wave_scan_incl_u32(mine, lane);
     if (lane == 63) wtot[par][wave] = inc;
     __syncthreads();   // (the other parity's slots are rewritten only after the next trip's barrier)
     unsigned long long cum = carry + (inc - mine), total = 0;
@@ -278,33 +249,22 @@ __global__ __launch_bounds__(SEL_THREADS) void surface_select_kernel(const unsig
   }
 }
 
-hipError_t zero(void* p, size_t bytes, hipStream_t st) { return hipMemsetAsync(p, 0, bytes, st); }
-
 // workspace of hdf_surface_distances, every part on a 256-byte boundary
 struct Carve {
   int64_t flags, d2T, d2P, scalars, hist, total;
   Carve(int D, int H, int W) {
     const int64_t V = (int64_t)D * H * W;
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
-    flags = 0;
-    d2T = flags + up(V);
-    d2P = d2T + up(V * 4);
-    scalars = d2P + up(V * 4);   // counts[5] uint64, then hd2 uint32 at byte 64
-    hist = scalars + 256;
-    total = hist + up(hdf_surface_hist_bins(D, H, W) * 4);
+    Carver c;
+    flags = c.take(V);
+    d2T = c.take(V * 4);
+    d2P = c.take(V * 4);
+    scalars = c.take(256);   // counts[5] uint64, then hd2 uint32 at byte 64
+    hist = c.take(hdf_surface_hist_bins(D, H, W) * 4);
+    total = c.at;
   }
 };
 }  // namespace
 
-int hdf_surface_check_dims(const char* who, int D, int H, int W) {
-  const int M = HDF_SURFACE_MAX_DIM;
-  HDF_CHECK_ARG(D >= 1 && D <= M && H >= 1 && H <= M && W >= 1 && W <= M, "surface: %s: volume %dx%dx%d (each of 1..%d)",
-                who, D, H, W, M);
-  // (belt and braces: with every dimension at most 1024 the product is at most 2^30; the kernels' 32-bit voxel arithmetic
-  // rests on this bound, so it is stated where the cap could one day be raised)
-  HDF_CHECK_ARG((int64_t)D * H * W < (1ll << 31), "surface: %s: %dx%dx%d has 2^31 voxels or more", who, D, H, W);
-  return HDF_OK;
-}
 int64_t hdf_surface_hist_bins(int D, int H, int W) {
   return (int64_t)(D - 1) * (D - 1) + (int64_t)(H - 1) * (H - 1) + (int64_t)(W - 1) * (W - 1) + 1;
 }
@@ -313,10 +273,7 @@ int64_t hdf_surface_ws_bytes(int D, int H, int W) { return Carve(D, H, W).total;
 int hdf_launch_mask_flags(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, uint8_t* flags,
                           unsigned long long* counts, bool counts_are_zero, hipStream_t st) {
   const int64_t V = (int64_t)D * H * W;
-  if (!counts_are_zero && zero(counts, 5 * sizeof(unsigned long long), st) != hipSuccess) {
-    hdf_set_error("surface: memset failed");
-    return HDF_ERR_HIP;
-  }
+  if (!counts_are_zero) HDF_TRY(hdf_zero_async("surface", counts, 5 * sizeof(unsigned long long), st));
   const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(V, 256), 8192);
   hipLaunchKernelGGL(mask_flags_kernel, dim3(gx), dim3(256), 0, st, tgt, pred, label, D, H, W, flags, counts);
   HDF_LAUNCH_CHECK();
@@ -373,10 +330,7 @@ int hdf_launch_surface_distances(const uint8_t* tgt, const uint8_t* pred, int la
   uint32_t* hd2 = (uint32_t*)(w + cv.scalars + 64);
   uint32_t* hist = (uint32_t*)(w + cv.hist);
   // the scalars and the histogram of an earlier call on this workspace are cleared on the stream, ahead of the kernels
-  if (zero(w + cv.scalars, (size_t)(cv.total - cv.scalars), st) != hipSuccess) {
-    hdf_set_error("surface: memset failed");
-    return HDF_ERR_HIP;
-  }
+  HDF_TRY(hdf_zero_async("surface", w + cv.scalars, (size_t)(cv.total - cv.scalars), st));
   HDF_TRY(hdf_launch_mask_flags(tgt, pred, label, D, H, W, flags, counts, true, st));
   HDF_TRY(hdf_launch_edt_sq(flags, HDF_SF_B26_T, D, H, W, d2T, st));
   HDF_TRY(hdf_launch_edt_sq(flags, HDF_SF_B26_P, D, H, W, d2P, st));
@@ -386,14 +340,6 @@ int hdf_launch_surface_distances(const uint8_t* tgt, const uint8_t* pred, int la
   hipLaunchKernelGGL(surface_select_kernel, dim3(1), dim3(SEL_THREADS), 0, st, counts, hd2, hist, (uint32_t)nbins,
                      (unsigned long long)V, result);
   HDF_LAUNCH_CHECK();
-  if (hist_out && hist_len > 0) {
-    const int64_t take = std::min(hist_len, nbins);
-    hipError_t e = hipMemcpyAsync(hist_out, hist, (size_t)take * 4, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && hist_len > take) e = zero(hist_out + take, (size_t)(hist_len - take) * 4, st);
-    if (e != hipSuccess) {
-      hdf_set_error("surface: histogram copy failed: %s", hipGetErrorString(e));
-      return HDF_ERR_HIP;
-    }
-  }
+  if (hist_out && hist_len > 0) HDF_TRY(hdf_copy_hist_out("surface", hist_out, hist_len, hist, nbins, st));
   return HDF_OK;
 }

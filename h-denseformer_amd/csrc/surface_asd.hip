@@ -15,19 +15,12 @@
 #include <algorithm>
 
 namespace {
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ------------------------------------------------------------------------------------------------ edge flags
 // E6(M): voxels of M with a face neighbour that is not in M; a neighbour outside the volume is not in M (this is where E6
 // and the C6 of mask_flags_kernel differ).  A voxel outside both masks costs two byte loads.
 __global__ __launch_bounds__(256) void edge_flags_kernel(const uint8_t* __restrict__ tgt, const uint8_t* __restrict__ pred,
                                                          int label, int D, int H, int W, uint8_t* __restrict__ flags,
                                                          unsigned long long* __restrict__ counts) {
-  __shared__ uint32_t red[4][2];
   const int64_t V = (int64_t)D * H * W;
   const uint32_t HW = (uint32_t)H * W;
   uint32_t cnt[2] = {0, 0};   // |E6(T)| |E6(P)|: a thread sees fewer than 2^31 voxels
@@ -56,15 +49,7 @@ __global__ __launch_bounds__(256) void edge_flags_kernel(const uint8_t* __restri
     flags[v] = (uint8_t)f;
     cnt[0] += (f & HDF_SF_E6_T) != 0, cnt[1] += (f & HDF_SF_E6_P) != 0;
   }
-  // per wave, per block, then one integer atomic per block and count
-  cnt[0] = wave_sum_u32(cnt[0]), cnt[1] = wave_sum_u32(cnt[1]);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = cnt[0], red[threadIdx.x >> 6][1] = cnt[1];
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const unsigned long long s = (unsigned long long)red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] +
-                                 red[3][threadIdx.x];
-    if (s) atomicAdd(counts + threadIdx.x, s);
-  }
+  block_add_counts(cnt, counts);
 }
 
 // ------------------------------------------------------------------------------------------------ gather
@@ -98,15 +83,7 @@ __global__ __launch_bounds__(256) void asd_gather_kernel(const uint8_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ the two sums
-// A fixed tree over the 256 threads of a workgroup: xor shuffles inside a wave, then the four waves in order.
-__device__ __forceinline__ double block_sum_f64(double v, double* wsum) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
+// (block_sum_f64, wave_ops.h: a fixed tree over the 256 threads of a workgroup)
 // Workgroup (blk, dir) adds the bins blk * 4096 .. + 4095 of direction dir: thread t the sixteen bins t, t + 256, ... of
 // that span in rising order (a chain of 16), then the tree (depth 8).  Most bins of a fair prediction are empty: they
 // cost no square root.
@@ -129,7 +106,8 @@ __global__ __launch_bounds__(256) void asd_partial_kernel(const uint32_t* __rest
 
 // One workgroup.  result[4] = |E6(T)| |E6(P)| bits(sum A) bits(sum B).  Thread t adds the partial sums t, t + 256, ... of
 // a direction (at most 3 * 1023^2 / 4096 / 256 + 1 = 3 of them), then the tree.  A direction has no distances when either
-// edge set is empty (nothing to measure from, or nothing to measure to): both sums are +0 then.
+// edge set is empty (nothing to measure from, or nothing to measure to): both sums are +0 then.  surface_mm.hip ends with
+// the same kernel (hdf_launch_asd_final) over the partial sums of its voxel runs.
 __global__ __launch_bounds__(256) void asd_final_kernel(const unsigned long long* __restrict__ counts,
                                                         const double* __restrict__ partial, uint32_t nblk,
                                                         unsigned long long* __restrict__ result) {
@@ -149,37 +127,39 @@ __global__ __launch_bounds__(256) void asd_final_kernel(const unsigned long long
   }
 }
 
-hipError_t zero(void* p, size_t bytes, hipStream_t st) { return hipMemsetAsync(p, 0, bytes, st); }
-
 // workspace of hdf_surface_asd, every part on a 256-byte boundary.  Through the scalars it is laid out like that of
 // hdf_surface_distances and it holds one histogram more, so it is never the smaller of the two.
 struct Carve {
   int64_t flags, d2ET, d2EP, scalars, hist, row, partial, nblk, total;
   Carve(int D, int H, int W) {
     const int64_t V = (int64_t)D * H * W, nbins = hdf_surface_hist_bins(D, H, W);
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
-    flags = 0;
-    d2ET = flags + up(V);
-    d2EP = d2ET + up(V * 4);
-    scalars = d2EP + up(V * 4);   // counts[2] uint64
-    hist = scalars + 256;
-    row = up(nbins * 4) / 4;      // entries from histogram A to histogram B
-    partial = hist + 2 * row * 4;
+    Carver c;
+    flags = c.take(V);
+    d2ET = c.take(V * 4);
+    d2EP = c.take(V * 4);
+    scalars = c.take(256);            // counts[2] uint64
+    row = up256(nbins * 4) / 4;       // entries from histogram A to histogram B
+    hist = c.take(2 * row * 4);
     nblk = ceil_div64(nbins, ASD_BINS_PER_BLOCK);
-    total = partial + up(2 * nblk * 8);
+    partial = c.take(2 * nblk * 8);
+    total = c.at;
   }
 };
 }  // namespace
+
+int hdf_launch_asd_final(const unsigned long long* counts, const double* partial, uint32_t nblk, unsigned long long* result,
+                         hipStream_t st) {
+  hipLaunchKernelGGL(asd_final_kernel, dim3(1), dim3(256), 0, st, counts, partial, nblk, result);
+  HDF_LAUNCH_CHECK();
+  return HDF_OK;
+}
 
 int64_t hdf_surface_asd_ws_bytes(int D, int H, int W) { return Carve(D, H, W).total; }
 
 int hdf_launch_edge_flags(const uint8_t* tgt, const uint8_t* pred, int label, int D, int H, int W, uint8_t* flags,
                           unsigned long long* counts, bool counts_are_zero, hipStream_t st) {
   const int64_t V = (int64_t)D * H * W;
-  if (!counts_are_zero && zero(counts, 2 * sizeof(unsigned long long), st) != hipSuccess) {
-    hdf_set_error("surface: memset failed");
-    return HDF_ERR_HIP;
-  }
+  if (!counts_are_zero) HDF_TRY(hdf_zero_async("surface", counts, 2 * sizeof(unsigned long long), st));
   const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(V, 256), 8192);
   hipLaunchKernelGGL(edge_flags_kernel, dim3(gx), dim3(256), 0, st, tgt, pred, label, D, H, W, flags, counts);
   HDF_LAUNCH_CHECK();
@@ -198,10 +178,7 @@ int hdf_launch_surface_asd(const uint8_t* tgt, const uint8_t* pred, int label, i
   double* partial = (double*)(w + cv.partial);
   // the counts and both histograms of an earlier call on this workspace are cleared on the stream, ahead of the kernels
   // (every partial sum is written before it is read)
-  if (zero(w + cv.scalars, (size_t)(cv.partial - cv.scalars), st) != hipSuccess) {
-    hdf_set_error("surface: memset failed");
-    return HDF_ERR_HIP;
-  }
+  HDF_TRY(hdf_zero_async("surface", w + cv.scalars, (size_t)(cv.partial - cv.scalars), st));
   HDF_TRY(hdf_launch_edge_flags(tgt, pred, label, D, H, W, flags, counts, true, st));
   HDF_TRY(hdf_launch_edt_sq(flags, HDF_SF_E6_T, D, H, W, d2ET, st));
   HDF_TRY(hdf_launch_edt_sq(flags, HDF_SF_E6_P, D, H, W, d2EP, st));
@@ -211,19 +188,9 @@ int hdf_launch_surface_asd(const uint8_t* tgt, const uint8_t* pred, int label, i
   hipLaunchKernelGGL(asd_partial_kernel, dim3((unsigned)cv.nblk, 2), dim3(256), 0, st, hist, cv.row, (uint32_t)nbins,
                      (uint32_t)cv.nblk, partial);
   HDF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(asd_final_kernel, dim3(1), dim3(256), 0, st, counts, partial, (uint32_t)cv.nblk, result);
-  HDF_LAUNCH_CHECK();
-  if (hist_out && hist_len > 0) {
-    const int64_t take = std::min(hist_len, nbins);
-    for (int dir = 0; dir < 2; dir++) {
-      uint32_t* dst = hist_out + dir * hist_len;
-      hipError_t e = hipMemcpyAsync(dst, hist + dir * cv.row, (size_t)take * 4, hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess && hist_len > take) e = zero(dst + take, (size_t)(hist_len - take) * 4, st);
-      if (e != hipSuccess) {
-        hdf_set_error("surface: histogram copy failed: %s", hipGetErrorString(e));
-        return HDF_ERR_HIP;
-      }
-    }
-  }
+  HDF_TRY(hdf_launch_asd_final(counts, partial, (uint32_t)cv.nblk, result, st));
+  if (hist_out && hist_len > 0)
+    for (int dir = 0; dir < 2; dir++)
+      HDF_TRY(hdf_copy_hist_out("surface", hist_out + dir * hist_len, hist_len, hist + dir * cv.row, nbins, st));
   return HDF_OK;
 }

@@ -9,7 +9,7 @@
 //   select_*_kernel       exact order statistics S[lo], S[lo + 1] over 64-bit keys: six radix passes (11 11 11 11 10 10 bits,
 //                         from the top), a one-workgroup pick between them, one pass for the smallest key above S[lo]
 //   asd_sum_mm_kernel     sum sqrt(D2) over either edge set: a block per contiguous run of voxels, a fixed tree inside it
-//   asd_final_mm_kernel   one workgroup: the partial sums in index order, result[4]
+//   (surface_asd.hip)     asd_final_kernel, one workgroup: the partial sums in index order, result[4]
 //
 // Exactness of the transform.  D2(v) = min over seeds of fl(fl(wz a^2) + fl(fl(wy b^2) + fl(wx c^2))) (include/hdf.h).  fl(x + y)
 // and fl(w k) are monotone in each argument, so the minimum over c^2 can be taken first (the row pass), then over b, then
@@ -118,11 +118,6 @@ int launch_col_mm(double* d2, int64_t outer, int L, int64_t inner, double w, dou
 // ------------------------------------------------------------------------------------------------ Hausdorff maximum
 // max(max over P \ T of D2_T, max over T \ P of D2_P) as a bit pattern; +inf (a map without seeds: such a call is not
 // valid) is not a distance.  *hd2 is 0 on entry.
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned long long)__shfl_xor(v, o, 64));
-  return v;
-}
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned long long)__shfl_xor(v, o, 64));
@@ -323,15 +318,7 @@ int run_select(const Src& src, int64_t items, void* ws, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------ the two ASD sums
-// A fixed tree over the 256 threads of a workgroup: xor shuffles inside a wave, then the four waves in order.
-__device__ __forceinline__ double block_sum_f64(double v, double* wsum) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
+// (block_sum_f64, wave_ops.h: a fixed tree over the 256 threads of a workgroup)
 // Workgroup b adds the voxels [b chunk, min(V, (b + 1) chunk)): thread t those at t, t + 256, ... of the run in rising
 // order, then the tree.  chunk and the number of workgroups follow from V alone (AsdSplit), so does the order of every sum.
 // A: sqrt(D2_ET) over E6(P) into partial[b], B: sqrt(D2_EP) over E6(T) into partial[nblk + b].
@@ -351,27 +338,8 @@ __global__ __launch_bounds__(256) void asd_sum_mm_kernel(const uint8_t* __restri
   if (threadIdx.x == 0) partial[blockIdx.x] = a, partial[gridDim.x + blockIdx.x] = b;
 }
 
-// One workgroup.  result[4] = |E6(T)| |E6(P)| bits(sum A) bits(sum B).  Thread t adds the partial sums t, t + 256, ... of a
-// direction, then the tree.  A direction has no distances when either edge set is empty (one map is all +inf): both sums
-// are +0 then.
-__global__ __launch_bounds__(256) void asd_final_mm_kernel(const unsigned long long* __restrict__ counts,
-                                                           const double* __restrict__ partial, uint32_t nblk,
-                                                           unsigned long long* __restrict__ result) {
-  __shared__ double wsum[2][4];
-  const bool any = counts[0] > 0 && counts[1] > 0;
-  double s[2];
-#pragma unroll
-  for (int dir = 0; dir < 2; dir++) {
-    double a = 0.0;
-    for (uint32_t b = threadIdx.x; b < nblk; b += 256) a += partial[dir * nblk + b];
-    s[dir] = block_sum_f64(a, wsum[dir]);
-  }
-  if (threadIdx.x == 0) {
-    result[0] = counts[0], result[1] = counts[1];
-    result[2] = bits_of(any ? s[0] : 0.0);
-    result[3] = bits_of(any ? s[1] : 0.0);
-  }
-}
+// The partial sums end in result[4] through surface_asd.hip's asd_final_kernel (hdf_launch_asd_final): in index order, both
+// sums +0 when either edge set is empty (one map is all +inf).
 
 // at most 4096 runs of a multiple of 256 voxels, at least 4096 voxels each
 struct AsdSplit {
@@ -389,24 +357,16 @@ struct CarveMm {
   int64_t flags, d2A, d2B, scalars, select, partial, total;
   CarveMm(int D, int H, int W) {
     const int64_t V = (int64_t)D * H * W;
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
-    flags = 0;
-    d2A = flags + up(V);
-    d2B = d2A + up(V * 8);
-    scalars = d2B + up(V * 8);   // counts[5] uint64, then the maximum (uint64) at byte 64
-    select = scalars + 256;
-    partial = select + up(HDF_SELECT_U64_WS);
-    total = partial + up(2 * AsdSplit(V).nblk * 8);
+    Carver c;
+    flags = c.take(V);
+    d2A = c.take(V * 8);
+    d2B = c.take(V * 8);
+    scalars = c.take(256);   // counts[5] uint64, then the maximum (uint64) at byte 64
+    select = c.take(HDF_SELECT_U64_WS);
+    partial = c.take(2 * AsdSplit(V).nblk * 8);
+    total = c.at;
   }
 };
-
-int zero_mm(void* p, size_t bytes, hipStream_t st) {
-  if (hipMemsetAsync(p, 0, bytes, st) != hipSuccess) {
-    hdf_set_error("surface: memset failed");
-    return HDF_ERR_HIP;
-  }
-  return HDF_OK;
-}
 }  // namespace
 
 int hdf_surface_check_spacing(const char* who, const double* spacing, SurfaceSpacing* out) {
@@ -431,7 +391,7 @@ int hdf_launch_edt_sq_mm(const uint8_t* flags, int seed_mask, int D, int H, int 
 
 int hdf_launch_select_u64(const unsigned long long* keys, int64_t n, int64_t lo, void* ws, unsigned long long* out2,
                           hipStream_t st) {
-  HDF_TRY(zero_mm(ws, HDF_SELECT_U64_WS, st));
+  HDF_TRY(hdf_zero_async("surface", ws, HDF_SELECT_U64_WS, st));
   SelState* state = reinterpret_cast<SelState*>(reinterpret_cast<char*>(ws) + SEL_OFF_STATE);
   hipLaunchKernelGGL(select_setup_kernel, dim3(1), dim3(1), 0, st, state, (unsigned long long)lo);
   HDF_TRY(run_select(ArrayKeys{keys, n}, n, ws, st));
@@ -451,7 +411,7 @@ int hdf_launch_surface_distances_mm(const uint8_t* tgt, const uint8_t* pred, int
   unsigned long long* hd2 = (unsigned long long*)(w + cv.scalars + 64);
   SelState* state = reinterpret_cast<SelState*>(w + cv.select + SEL_OFF_STATE);
   // the scalars and the select's state of an earlier call on this workspace are cleared on the stream, ahead of the kernels
-  HDF_TRY(zero_mm(w + cv.scalars, (size_t)(cv.partial - cv.scalars), st));
+  HDF_TRY(hdf_zero_async("surface", w + cv.scalars, (size_t)(cv.partial - cv.scalars), st));
   HDF_TRY(hdf_launch_mask_flags(tgt, pred, label, D, H, W, flags, counts, true, st));
   HDF_TRY(hdf_launch_edt_sq_mm(flags, HDF_SF_B26_T, D, H, W, sp, d2T, st));
   HDF_TRY(hdf_launch_edt_sq_mm(flags, HDF_SF_B26_P, D, H, W, sp, d2P, st));
@@ -476,13 +436,12 @@ int hdf_launch_surface_asd_mm(const uint8_t* tgt, const uint8_t* pred, int label
   unsigned long long* counts = (unsigned long long*)(w + cv.scalars);
   double* partial = (double*)(w + cv.partial);
   // the counts of an earlier call are cleared on the stream (every partial sum is written before it is read)
-  HDF_TRY(zero_mm(w + cv.scalars, 256, st));
+  HDF_TRY(hdf_zero_async("surface", w + cv.scalars, 256, st));
   HDF_TRY(hdf_launch_edge_flags(tgt, pred, label, D, H, W, flags, counts, true, st));
   HDF_TRY(hdf_launch_edt_sq_mm(flags, HDF_SF_E6_T, D, H, W, sp, d2ET, st));
   HDF_TRY(hdf_launch_edt_sq_mm(flags, HDF_SF_E6_P, D, H, W, sp, d2EP, st));
   hipLaunchKernelGGL(asd_sum_mm_kernel, dim3((unsigned)split.nblk), dim3(256), 0, st, flags, d2ET, d2EP, V, split.chunk,
                      partial);
-  hipLaunchKernelGGL(asd_final_mm_kernel, dim3(1), dim3(256), 0, st, counts, partial, (uint32_t)split.nblk, result);
   HDF_LAUNCH_CHECK();
-  return HDF_OK;
+  return hdf_launch_asd_final(counts, partial, (uint32_t)split.nblk, result, st);
 }

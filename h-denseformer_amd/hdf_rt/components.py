@@ -14,50 +14,28 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
+from ._volume import WorkspaceCache, as_volume, check_out, clear_all
 
 TABLE_COLS = ("size", "value", "first", "zmin", "zmax", "ymin", "ymax", "xmin", "xmax")
-# (device, stream, D, H, W) -> uint8 tensor, like surface._workspaces: about 5 bytes a voxel, one per volume shape and
-# stream, never evicted -- clear_workspaces() (here or in hdf_rt.surface) gives the memory back
-_workspaces = {}
+# one workspace per volume shape and stream (_volume.WorkspaceCache), about 5 bytes a voxel, in a cache of its own
+_workspaces = WorkspaceCache("hdf_cc_workspace_bytes")
 
 
 def clear_workspaces():
-    _workspaces.clear()
+    """drop the cached workspaces: these, and those of the other entries on a volume (as hdf_rt.surface's)"""
+    clear_all()
 
 
 def _volume(a, what="volume"):
     """(uint8 [D][H][W] on the GPU, the caller's shape) from a device tensor or a numpy array, uint8 or bool, 3-D or 2-D"""
-    if not torch.cuda.is_available():
-        raise _lib.HdfError("connected components need a GPU (there is no CPU path)")
-    if not torch.is_tensor(a):
-        a = torch.from_numpy(np.ascontiguousarray(a))
-    if a.dim() not in (2, 3):
-        raise ValueError(f"{what} must be [D, H, W] or [H, W], got {tuple(a.shape)}")
-    if a.dtype not in (torch.uint8, torch.bool):
-        raise ValueError(f"{what} must be uint8 or bool, got {a.dtype}")
-    shape = tuple(a.shape)
-    if a.device.type != "cuda":
-        a = a.to("cuda")            # uploaded once
-    a = a.to(torch.uint8).contiguous()
-    return (a[None] if a.dim() == 2 else a), shape
-
-
-def _workspace(dev, shape):
-    key = (str(dev), stream_ptr()) + shape
-    ws = _workspaces.get(key)
-    if ws is None:
-        n = lib().hdf_cc_workspace_bytes(*shape)
-        if n < 0:
-            raise _lib.HdfError("hdf_cc_workspace_bytes: " + lib().hdf_last_error().decode(errors="replace"))
-        ws = _workspaces[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-    return ws
+    return as_volume(a, what, dims=(2, 3), dtypes=(torch.uint8, torch.bool), who="connected components need")
 
 
 def _label(vol, connectivity, label):
     """(ids int32 [D, H, W], result int64[2] = n, foreground voxels), both on the device"""
     shape = tuple(int(s) for s in vol.shape)
     with torch.cuda.device(vol.device):
-        ws = _workspace(vol.device, shape)
+        ws = _workspaces.workspace(vol.device, *shape)
         ids = torch.empty(shape, dtype=torch.int32, device=vol.device)
         res = torch.empty(2, dtype=torch.int64, device=vol.device)
         check(lib().hdf_cc_label(ptr(vol), int(label), int(connectivity), *shape, ptr(ids), ptr(res), ptr(ws), ws.numel(),
@@ -125,15 +103,9 @@ def _filter(volume, connectivity, label, min_size, keep_largest, out):
     vol, shape = _volume(volume)
     dims = tuple(int(s) for s in vol.shape)
     ids, _ = _label(vol, connectivity, label)
-    if out is None:
-        dst = torch.empty_like(vol)
-    else:
-        if not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == vol.device and out.is_contiguous()
-                and tuple(out.shape) == shape):
-            raise ValueError("out must be a contiguous uint8 device tensor shaped like the volume")
-        dst = out.view(dims)
+    dst = check_out(out, vol, shape)
     with torch.cuda.device(vol.device):
-        ws = _workspace(vol.device, dims)
+        ws = _workspaces.workspace(vol.device, *dims)
         res = torch.empty(2, dtype=torch.int64, device=vol.device)
         check(lib().hdf_cc_filter(ptr(vol), ptr(ids), *dims, int(min_size), int(keep_largest), ptr(dst), ptr(res), ptr(ws),
                                   ws.numel(), stream_ptr()), "hdf_cc_filter")

@@ -13,29 +13,25 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
-from .components import _label, _volume, component_table
+from ._volume import WorkspaceCache, as_volume, clear_all
+from .components import _label, component_table
 from .morphology import binary_dilation
 
 PAIRS_A0, PAIRS_B0 = 1, 2            # HDF_PAIRS_*
 PAIR_COLS = ("a", "b", "n", "m")
-# (device, stream, capacity) -> uint8 tensor, like components._workspaces: 256 + 24 bytes a table slot (a power of two >=
-# 2 * capacity), one per capacity and stream, never evicted -- clear_workspaces() gives the memory back
-_workspaces = {}
+# one workspace per capacity and stream (_volume.WorkspaceCache): 256 + 24 bytes a table slot (a power of two >=
+# 2 * capacity), in a cache of its own
+_workspaces = WorkspaceCache("hdf_cc_pairs_workspace_bytes")
 
 
 def clear_workspaces():
-    _workspaces.clear()
+    """drop the cached workspaces: these, and those of the other entries on a volume (as hdf_rt.surface's)"""
+    clear_all()
 
 
-def _workspace(dev, capacity):
-    key = (str(dev), stream_ptr(), capacity)
-    ws = _workspaces.get(key)
-    if ws is None:
-        n = lib().hdf_cc_pairs_workspace_bytes(capacity)
-        if n < 0:
-            raise _lib.HdfError("hdf_cc_pairs_workspace_bytes: " + lib().hdf_last_error().decode(errors="replace"))
-        ws = _workspaces[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-    return ws
+def _volume(a, what):
+    """a uint8 or bool map as components takes it: (uint8 [D][H][W] on the GPU, the caller's shape)"""
+    return as_volume(a, what, dtypes=(torch.uint8, torch.bool), who="connected components need")
 
 
 def _ids(t, what):
@@ -65,7 +61,7 @@ def component_overlap(ids_a, ids_b, mask=None, capacity=4096, zero_a=False, zero
     capacity = int(capacity)
     flags = (PAIRS_A0 if zero_a else 0) | (PAIRS_B0 if zero_b else 0)
     with torch.cuda.device(a.device):
-        ws = _workspace(a.device, capacity)
+        ws = _workspaces.workspace(a.device, capacity)
         pairs = torch.empty((capacity, 4), dtype=torch.int64, device=a.device)
         res = torch.empty(4, dtype=torch.int64, device=a.device)
         check(lib().hdf_cc_pairs(ptr(a), ptr(b), ptr(mask), flags, *shape, capacity, ptr(pairs), ptr(res), ptr(ws), ws.numel(),

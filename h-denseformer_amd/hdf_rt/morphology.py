@@ -8,51 +8,35 @@ connectivity is 6, 18 or 26 (scipy's generate_binary_structure(3, 1 | 2 | 3)); l
 mask, label = k only the voxels equal to k; border_value is what a voxel outside the volume reads as; iterations is the
 number of steps, 1..256 (scipy's "until nothing changes", iterations < 1, is refused).  A [H, W] input is the depth-1
 volume [1, H, W]: 6 / 18 / 26 are then the 4- / 8- / 8-neighbourhood and there is no z border.  The defaults are scipy's."""
+import collections
+
 import torch
 
-from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
-from .components import _volume
+from ._volume import WorkspaceCache, as_volume, check_out, clear_all
 
 DILATE, ERODE, OPEN, CLOSE = 0, 1, 2, 3      # HDF_MORPH_*
 MASK, MAP = 0, 1
 OPS = {"dilate": DILATE, "erode": ERODE, "open": OPEN, "close": CLOSE}
-# (entry, device, stream, D, H, W) -> uint8 tensor, like components._workspaces: a quarter of a byte a voxel for the four
-# ops, about 11 bytes a voxel for fill holes, one per volume shape and stream, never evicted -- clear_workspaces() (here or
-# in hdf_rt.surface) gives the memory back
-_workspaces = {}
+# one workspace per entry, volume shape and stream (_volume.WorkspaceCache): a quarter of a byte a voxel for the four ops,
+# about 11 bytes a voxel for fill holes, each in a cache of its own
+_morph_workspaces = WorkspaceCache("hdf_morph_workspace_bytes")
+_fill_workspaces = WorkspaceCache("hdf_fill_holes_workspace_bytes")
+_workspaces = collections.ChainMap(_morph_workspaces, _fill_workspaces)      # both, for a reader
 
 
 def clear_workspaces():
-    _workspaces.clear()
+    """drop the cached workspaces: these, and those of the other entries on a volume (as hdf_rt.surface's)"""
+    clear_all()
 
 
-def _workspace(size_fn, dev, shape):
-    key = (size_fn, str(dev), stream_ptr()) + shape
-    ws = _workspaces.get(key)
-    if ws is None:
-        n = getattr(lib(), size_fn)(*shape)
-        if n < 0:
-            raise _lib.HdfError(size_fn + ": " + lib().hdf_last_error().decode(errors="replace"))
-        ws = _workspaces[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-    return ws
-
-
-def _run(volume, out, return_counts, size_fn, call):
+def _run(volume, out, return_counts, cache, call):
     """call(vol, dims, dst, res, ws) enqueues one entry; returns the uint8 tensor shaped like `volume` (and the counts)"""
-    if not torch.cuda.is_available():
-        raise _lib.HdfError("morphology needs a GPU (there is no CPU path)")
-    vol, shape = _volume(volume)
+    vol, shape = as_volume(volume, "volume", dtypes=(torch.uint8, torch.bool), who="morphology needs")
     dims = tuple(int(s) for s in vol.shape)
-    if out is None:
-        dst = torch.empty_like(vol)
-    else:
-        if not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == vol.device and out.is_contiguous()
-                and tuple(out.shape) == shape):
-            raise ValueError("out must be a contiguous uint8 device tensor shaped like the volume")
-        dst = out.view(dims)
+    dst = check_out(out, vol, shape)
     with torch.cuda.device(vol.device):
-        ws = _workspace(size_fn, vol.device, dims)
+        ws = cache.workspace(vol.device, *dims)
         res = torch.empty(2, dtype=torch.int64, device=vol.device)
         call(vol, dims, dst, res, ws)
     return (dst.view(shape), res) if return_counts else dst.view(shape)
@@ -62,14 +46,14 @@ def _morph(volume, op, connectivity, iterations, label, border_value, mode, out,
     def call(vol, dims, dst, res, ws):
         check(lib().hdf_morph(ptr(vol), int(label), int(op), int(connectivity), int(iterations), int(border_value), mode, *dims,
                               ptr(dst), ptr(res), ptr(ws), ws.numel(), stream_ptr()), "hdf_morph")
-    return _run(volume, out, return_counts, "hdf_morph_workspace_bytes", call)
+    return _run(volume, out, return_counts, _morph_workspaces, call)
 
 
 def _fill(volume, connectivity, label, mode, out, return_counts):
     def call(vol, dims, dst, res, ws):
         check(lib().hdf_fill_holes(ptr(vol), int(label), int(connectivity), mode, *dims, ptr(dst), ptr(res), ptr(ws), ws.numel(),
                                    stream_ptr()), "hdf_fill_holes")
-    return _run(volume, out, return_counts, "hdf_fill_holes_workspace_bytes", call)
+    return _run(volume, out, return_counts, _fill_workspaces, call)
 
 
 def binary_dilation(volume, connectivity=6, iterations=1, label=0, border_value=0, out=None, return_counts=False):

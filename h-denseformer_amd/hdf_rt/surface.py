@@ -20,58 +20,29 @@ import struct
 import numpy as np
 import torch
 
-from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
+from ._volume import WorkspaceCache, as_volume, clear_all
 
 KEYS = ("Jaccard", "Dice", "VolumeSimilarity", "HausdorffDistance", "HausdorffDistance95")
-# (device, stream, D, H, W) -> uint8 tensor: one workspace per volume shape and stream.  A workspace is reused by the next
-# call on ITS stream (the kernels of two calls are ordered there); callers on two streams get one each and do not race.
-# About 9 bytes a voxel plus the histogram; nothing is evicted -- clear_workspaces() gives the memory back.
-_workspaces = {}
+# one workspace per volume shape and stream (_volume.WorkspaceCache): about 9 bytes a voxel plus the histogram
+_workspaces = WorkspaceCache("hdf_surface_workspace_bytes")
 # the same for hdf_surface_asd, which needs one histogram more: a cache of its own, so that neither call is ever handed
 # the other's allocation
-_asd_workspaces = {}
+_asd_workspaces = WorkspaceCache("hdf_surface_asd_workspace_bytes")
 # and for the entries that take a spacing (fp64 maps: about 17 bytes a voxel), shared by the two of them
-_mm_workspaces = {}
+_mm_workspaces = WorkspaceCache("hdf_surface_mm_workspace_bytes")
 ASD_KEYS = ("ASD", "ASD_pred_to_gt", "ASD_gt_to_pred")
 
 
 def clear_workspaces():
-    """drop the cached workspaces (a caller that is done scoring, or moves on to another volume shape)"""
-    _workspaces.clear()
-    _asd_workspaces.clear()
-    _mm_workspaces.clear()
-    from . import components
-    components.clear_workspaces()      # the connected-component entries keep a cache of their own
-    from . import morphology
-    morphology.clear_workspaces()      # and so do the morphology entries
-    from . import lesions
-    lesions.clear_workspaces()         # and the overlap table
+    """drop the cached workspaces (a caller that is done scoring, or moves on to another volume shape): these, and those
+    of the connected-component, morphology and overlap-table entries"""
+    clear_all()
 
 
 def _volume(a, what):
-    """uint8 [D][H][W] on the GPU from a device tensor or a numpy array (uploaded once)"""
-    if not torch.cuda.is_available():
-        raise _lib.HdfError("surface metrics need a GPU (there is no CPU path)")
-    if not torch.is_tensor(a):
-        a = torch.from_numpy(np.ascontiguousarray(a))
-    if a.dim() != 3:
-        raise ValueError(f"{what} must be [D, H, W], got {tuple(a.shape)}")
-    if a.device.type != "cuda":
-        a = a.to("cuda")
-    return a.to(torch.uint8).contiguous()
-
-
-def _workspace(dev, shape, cache=None, size_fn="hdf_surface_workspace_bytes"):
-    cache = _workspaces if cache is None else cache
-    key = (str(dev), stream_ptr()) + shape
-    ws = cache.get(key)
-    if ws is None:
-        n = getattr(lib(), size_fn)(*shape)
-        if n < 0:
-            raise _lib.HdfError(size_fn + ": " + lib().hdf_last_error().decode(errors="replace"))
-        ws = cache[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-    return ws
+    """uint8 [D][H][W] on the GPU from a device tensor or a numpy array of any dtype (uploaded once)"""
+    return as_volume(a, what, dims=(3,), who="surface metrics need")[0]
 
 
 def _spacing(spacing):
@@ -131,7 +102,7 @@ def surface_scores(target, prediction, labels, spacing=None):
     if spacing is not None:
         sp = _spacing(spacing)
         with torch.cuda.device(tgt.device):
-            ws = _workspace(tgt.device, shape, _mm_workspaces, "hdf_surface_mm_workspace_bytes")
+            ws = _mm_workspaces.workspace(tgt.device, *shape)
             rows = torch.empty((max(len(labels), 1), 12), dtype=torch.int64, device=tgt.device)
             for i, k in enumerate(labels):
                 check(lib().hdf_surface_distances_mm(ptr(tgt), ptr(prd), k, *shape, sp, ptr(ws), ws.numel(), ptr(rows[i]),
@@ -139,7 +110,7 @@ def surface_scores(target, prediction, labels, spacing=None):
             host = rows.cpu()          # the one D2H copy, after every class is enqueued
         return [scores_from_result_mm(host[i].tolist()) for i in range(len(labels))]
     with torch.cuda.device(tgt.device):
-        ws = _workspace(tgt.device, shape)
+        ws = _workspaces.workspace(tgt.device, *shape)
         rows = torch.empty((max(len(labels), 1), 12), dtype=torch.int64, device=tgt.device)
         for i, k in enumerate(labels):
             check(lib().hdf_surface_distances(ptr(tgt), ptr(prd), k, *shape, ptr(ws), ws.numel(), ptr(rows[i]), None, 0,
@@ -208,7 +179,7 @@ def asd_scores(target, prediction, labels, spacing=None):
     if spacing is not None:
         sp = _spacing(spacing)
         with torch.cuda.device(tgt.device):
-            ws = _workspace(tgt.device, shape, _mm_workspaces, "hdf_surface_mm_workspace_bytes")
+            ws = _mm_workspaces.workspace(tgt.device, *shape)
             rows = torch.empty((max(len(labels), 1), 4), dtype=torch.int64, device=tgt.device)
             for i, k in enumerate(labels):
                 check(lib().hdf_surface_asd_mm(ptr(tgt), ptr(prd), k, *shape, sp, ptr(ws), ws.numel(), ptr(rows[i]),
@@ -216,7 +187,7 @@ def asd_scores(target, prediction, labels, spacing=None):
             host = rows.cpu()          # the one D2H copy, after every class is enqueued
         return [asd_from_result(host[i].tolist()) for i in range(len(labels))]
     with torch.cuda.device(tgt.device):
-        ws = _workspace(tgt.device, shape, _asd_workspaces, "hdf_surface_asd_workspace_bytes")
+        ws = _asd_workspaces.workspace(tgt.device, *shape)
         rows = torch.empty((max(len(labels), 1), 4), dtype=torch.int64, device=tgt.device)
         for i, k in enumerate(labels):
             check(lib().hdf_surface_asd(ptr(tgt), ptr(prd), k, *shape, ptr(ws), ws.numel(), ptr(rows[i]), None, 0,

@@ -301,13 +301,14 @@ class _Recorder:
 def test_spacing_none_never_touches_the_new_entries(monkeypatch):
     """the wrappers with the library, the device pointers and the stream replaced by stand-ins, on host tensors: None
     (given or left out) calls exactly the entries the parent commit called; a triple calls the _mm ones"""
-    from hdf_rt import surface
+    from hdf_rt import _volume, surface
     rec = _Recorder()
-    monkeypatch.setattr(surface, "lib", lambda: rec)
-    monkeypatch.setattr(surface, "stream_ptr", lambda: 0)
+    for mod in (surface, _volume):              # (the workspace caches of surface live in _volume.WorkspaceCache)
+        monkeypatch.setattr(mod, "lib", lambda: rec)
+        monkeypatch.setattr(mod, "stream_ptr", lambda: 0)
     monkeypatch.setattr(surface, "_volume", lambda a, what: torch.as_tensor(np.ascontiguousarray(a)).to(torch.uint8))
-    monkeypatch.setattr(surface, "_workspace", lambda dev, shape, cache=None, size_fn="hdf_surface_workspace_bytes":
-                        (rec.called.append(size_fn), torch.zeros(8, dtype=torch.uint8))[1])
+    for cache in (surface._workspaces, surface._asd_workspaces, surface._mm_workspaces):
+        monkeypatch.setattr(cache, "get", lambda key, default=None: None)      # every call asks the library for the size
 
     class _NoDevice:
         def __init__(self, *_a):
@@ -338,6 +339,7 @@ def test_spacing_none_never_touches_the_new_entries(monkeypatch):
     assert set(rec.called) == {"hdf_surface_mm_workspace_bytes", "hdf_surface_asd_mm"}, rec.called
     with pytest.raises(ValueError):
         surface.multi_hd(t, p, 2, spacing=(1.0, 1.0))
+    surface.clear_workspaces()                  # the stand-in workspaces are host tensors: nothing later may find them
 
 
 def test_scores_from_result_mm_reads_bit_patterns():
