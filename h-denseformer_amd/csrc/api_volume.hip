@@ -1,11 +1,13 @@
 // The C ABI of the entries on a uint8 / int32 volume [D][H][W]: surface distances and the average surface distance, in
 // voxels and in physical units (surface.hip, surface_asd.hip, surface_mm.hip), connected components (components.hip), the
-// overlap table of two id maps (cc_pairs.hip) and binary morphology (morphology.hip).  Every entry checks its arguments on
+// overlap table of two id maps (cc_pairs.hip), per-lesion surface distances on crops (lesion_surface.hip) and binary
+// morphology (morphology.hip).  Every entry checks its arguments on
 // the host -- the first check that fails decides the message, "<family>: <entry>: ..." -- and hands on to the unit's
 // launcher.  Nothing here touches a plan.
 #include "../../include/hdf.h"
 #include "cc_pairs.h"
 #include "components.h"
+#include "lesion_surface.h"
 #include "morphology.h"
 #include "surface.h"
 
@@ -239,6 +241,45 @@ int hdf_cc_pairs(const int32_t* ids_a, const int32_t* ids_b, const uint8_t* mask
   }
   return hdf_launch_cc_pairs(ids_a, ids_b, mask, flags, D, H, W, capacity, (long long*)pairs, (unsigned long long*)result,
                              workspace, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------- per-lesion surface distances
+// lesions is a host pointer: its rows are checked, and read, before anything else that depends on them.
+int64_t hdf_lesion_surface_workspace_bytes(const int32_t* lesions, int64_t L, int D, int H, int W, int mm) {
+  LesionPlan plan;
+  const char* who = "lesion_workspace_bytes";
+  if (hdf_vol_check_dims(SURF, who, D, H, W) != HDF_OK) return -1;
+  if (L < 0 || (L > 0 && !lesions) || (mm != 0 && mm != 1)) {
+    hdf_set_error("surface: %s: L = %lld, lesions %s, mm = %d (L >= 0, rows for L > 0, mm 0 or 1)", who, (long long)L,
+                  lesions ? "given" : "null", mm);
+    return -1;
+  }
+  return hdf_lesion_surface_plan(who, lesions, L, D, H, W, mm != 0, &plan) == HDF_OK ? plan.total : -1;
+}
+int hdf_lesion_surface(const int32_t* ids_pred, const int32_t* ids_truth, const uint8_t* truth_mask, int D, int H, int W,
+                       const int64_t* pairs, int64_t n_pairs, const int32_t* lesions, int64_t L, const double* spacing,
+                       void* workspace, int64_t workspace_bytes, uint64_t* results, hdf_stream stream) {
+  const char* who = "lesion_surface";
+  SurfaceSpacing sp;
+  if (spacing) HDF_TRY(hdf_surface_check_spacing(who, spacing, &sp));
+  HDF_TRY(hdf_vol_check_dims(SURF, who, D, H, W));
+  HDF_CHECK_ARG(L >= 0 && n_pairs >= 0, "surface: %s: L = %lld, n_pairs = %lld (neither may be negative)", who, (long long)L,
+                (long long)n_pairs);
+  HDF_TRY(check_nonnull(SURF, who, ids_pred && ids_truth && truth_mask && (n_pairs == 0 || pairs) && (L == 0 || (lesions && results))));
+  LesionPlan plan;
+  HDF_TRY(hdf_lesion_surface_plan(who, lesions, L, D, H, W, spacing != nullptr, &plan));
+  if (L == 0) return HDF_OK;   // nothing to carve, nothing to write
+  HDF_TRY(check_workspace(SURF, who, workspace, workspace_bytes, plan.total));
+  const int64_t V = (int64_t)D * H * W, rows = L * 12 * 8;
+  HDF_TRY(check_disjoint(SURF, who, results, rows, workspace, plan.total, "results overlaps the workspace"));
+  const struct { const void* p; int64_t n; } in[4] = {{ids_pred, V * 4}, {ids_truth, V * 4}, {truth_mask, V}, {pairs, n_pairs * 32}};
+  for (int i = 0; i < 4; i++) {
+    if (!in[i].p) continue;
+    HDF_TRY(check_disjoint(SURF, who, results, rows, in[i].p, in[i].n, "results overlaps an input"));
+    HDF_TRY(check_disjoint(SURF, who, workspace, plan.total, in[i].p, in[i].n, "workspace overlaps an input"));
+  }
+  return hdf_launch_lesion_surface(ids_pred, ids_truth, truth_mask, H, W, (const long long*)pairs, n_pairs, plan,
+                                   spacing ? &sp : nullptr, workspace, (unsigned long long*)results, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------- binary morphology

@@ -1,12 +1,17 @@
 """Lesion-wise matching on the device: the overlap table of two labelings and the two per-lesion protocols built on it --
 detection matching (PI-CAI style: a predicted lesion is a hit when it overlaps a ground-truth lesion enough, its
-confidence is the peak probability inside it) and the BraTS-2023 lesion-wise Dice.  What a user does today with two copies
-of int32 id maps to the host (2 x 470 MB for a 448x512x512 volume) and np.unique over 64-bit keys on one thread.  Every
+confidence is the peak probability inside it) and the BraTS-2023 lesion-wise Dice and HD95.  What a user does today with two
+copies of int32 id maps to the host (2 x 470 MB for a 448x512x512 volume) and np.unique over 64-bit keys on one thread.  Every
 function labels, dilates and joins on the device and makes ONE copy to the host, of a table of a few thousand words.
-Kernels: csrc/cc_pairs.hip (and components.hip, morphology.hip); definitions: include/hdf.h.  No CPU fallback.
+The lesion-wise HD95 (lesion_wise_scores(hd95=True): per kept truth lesion `surface`, `hd` and `hd95`, at the top
+`lesion_hd95`, a missed lesion and a false positive scoring `hd95_penalty`) carves every lesion's box out of the id maps
+and runs the surface entry on the crops (hdf_lesion_surface); it makes a second copy, of twelve words a lesion.
+Kernels: csrc/cc_pairs.hip, csrc/lesion_surface.hip (and components.hip, morphology.hip, surface.hip); definitions:
+include/hdf.h.  No CPU fallback.
 
 connectivity, label and the numbering of the components are those of hdf_rt.components: ids 1..n in ascending order of
 each component's smallest linear voxel index.  A [H, W] input is the depth-1 volume [1, H, W]."""
+import ctypes
 import struct
 
 import torch
@@ -16,6 +21,7 @@ from ._lib import check, lib, ptr, stream_ptr
 from ._volume import WorkspaceCache, as_volume, clear_all
 from .components import _label, component_table
 from .morphology import binary_dilation
+from .surface import _spacing, scores_from_result, scores_from_result_mm
 
 PAIRS_A0, PAIRS_B0 = 1, 2            # HDF_PAIRS_*
 PAIR_COLS = ("a", "b", "n", "m")
@@ -140,9 +146,27 @@ def match_components(pred, truth, connectivity=26, pred_label=0, truth_label=0, 
                 truth_size=size_t[1:], confidence=conf)
 
 
+def _lesion_surfaces(ids_p, ids_t, g, pairs, n_pairs, boxes, spacing):
+    """hdf_lesion_surface for the rows `boxes` = [(j, zmin, zmax, ymin, ymax, xmin, xmax)]: the result rows as lists of twelve
+    ints, after ONE copy to the host.  One allocation of the size the entry asks for; it is not kept."""
+    shape = tuple(int(s) for s in ids_p.shape)
+    L = len(boxes)
+    rows7 = (ctypes.c_int32 * (7 * L))(*[int(v) for row in boxes for v in row])
+    sp = None if spacing is None else _spacing(spacing)
+    with torch.cuda.device(ids_p.device):
+        need = lib().hdf_lesion_surface_workspace_bytes(rows7, L, *shape, 0 if sp is None else 1)
+        if need < 0:
+            raise _lib.HdfError("hdf_lesion_surface_workspace_bytes: " + lib().hdf_last_error().decode(errors="replace"))
+        ws = torch.empty(need, dtype=torch.uint8, device=ids_p.device)
+        results = torch.empty((L, 12), dtype=torch.int64, device=ids_p.device)
+        check(lib().hdf_lesion_surface(ptr(ids_p), ptr(ids_t), ptr(g), *shape, ptr(pairs), n_pairs, rows7, L, sp, ptr(ws),
+                                       ws.numel(), ptr(results), stream_ptr()), "hdf_lesion_surface")
+        return results.cpu().tolist()          # the second and last D2H copy
+
+
 def lesion_wise_scores(pred, truth, label, dilate_iterations=3, dilate_connectivity=18, connectivity=26, min_size=0,
-                       capacity=4096):
-    """The BraTS-2023 lesion-wise Dice of class `label` (1..255).  G = truth == label; Gd = G dilated dilate_iterations
+                       capacity=4096, hd95=False, spacing=None, hd95_penalty=374.0):
+    """The BraTS-2023 lesion-wise Dice of class `label` (1..255), and with hd95=True its lesion-wise HD95.  G = truth == label; Gd = G dilated dilate_iterations
     times under dilate_connectivity (hdf_rt.binary_dilation; 0 iterations: Gd = G); the truth lesions are the components of
     Gd, the predicted lesions those of pred == label, both under `connectivity`.  One overlap table with mask = G and both
     zero flags, ONE copy to the host.  For truth lesion j:
@@ -154,10 +178,30 @@ def lesion_wise_scores(pred, truth, label, dilate_iterations=3, dilate_connectiv
 
     Returns a dict: lesions = per kept truth lesion a dict (id, gt, tp, pred = the ids of P_j, pred_voxels, dice),
     dropped = the ids of the dropped truth lesions, false_positives = the predicted ids in no P_j, fp, lesion_dice.
-    The per-lesion HD95 of the BraTS protocol is out of scope: it is not computed here."""
+
+    hd95=False is exactly that: the same dict from the same launches and the same single copy.  hd95=True adds the
+    protocol's second number.  The two component tables (hdf_cc_table) join the one copy; the box of lesion j is the union
+    of the box of truth lesion j and of the boxes of P_j; then ONE hdf_lesion_surface call for the kept lesions with a
+    non-empty P_j -- the masks (gt_j, P_j) carved on their boxes grown by one voxel, hdf_surface_distances on every crop --
+    and a second and last copy, of its twelve words a lesion.  The crop is exact: every seed, contour voxel and neighbour of
+    a mask voxel lies inside it, a clamped side is the volume's face, an unclamped one is true background, and a mask fills
+    the crop only if it fills the volume -- the words are those of the full-volume call.  spacing: None (voxels) or
+    (sz, sy, sx) as hdf_rt.surface takes it (hdf_surface_distances_mm); without hd95=True it is a ValueError.
+    Every kept lesion's dict gains surface (the twelve ints), hd and hd95 (surface.scores_from_result / _mm: the Hausdorff
+    distance and its 95th percentile, in voxels or in the spacing's unit).  A kept lesion with an empty P_j has surface =
+    None and hd = hd95 = hd95_penalty.  A lesion whose masks the surface entry calls invalid (gt_j or P_j fills the
+    volume) has hd = hd95 = NaN in its own dict and counts as hd95_penalty in the aggregate.  The top level gains
+    lesion_hd95 = (the sum of hd95 over the kept lesions + hd95_penalty * fp) / (kept truth lesions + fp), 0.0 when there
+    is neither.  All in fp64.  surface[0] and surface[1] must equal gt and pred_voxels of the overlap table: an HdfError
+    names the lesion where they do not (a box that did not contain its lesion)."""
     label, capacity, iters = int(label), int(capacity), int(dilate_iterations)
     if not 1 <= label <= 255:
         raise ValueError(f"label must be in 1..255, got {label}")
+    if spacing is not None:
+        if not hd95:
+            raise ValueError("spacing is the unit of the lesion-wise HD95: pass hd95=True with it")
+        _spacing(spacing)
+    penalty = float(hd95_penalty)
     pv, _ = _volume(pred, "pred")
     tv, _ = _volume(truth, "truth")
     if pv.shape != tv.shape:
@@ -168,7 +212,10 @@ def lesion_wise_scores(pred, truth, label, dilate_iterations=3, dilate_connectiv
     ids_p, res_p = _label(pv, connectivity, label)
     ids_t, res_t = _label(gd, connectivity, 0)
     pairs, res = component_overlap(ids_p, ids_t, g, capacity, True, True)
-    host = torch.cat([res, pairs.reshape(-1), res_p, res_t]).cpu().tolist()          # the one D2H copy
+    parts = [res, pairs.reshape(-1), res_p, res_t]
+    if hd95:
+        parts += [component_table(pv, ids_p, None, capacity).reshape(-1), component_table(gd, ids_t, None, capacity).reshape(-1)]
+    host = torch.cat(parts).cpu().tolist()          # the one D2H copy (with hd95: the first of two)
     rows = _rows(host, "lesion_wise_scores", capacity)
     tail = 4 + 4 * capacity
     n_pred, n_truth = host[tail], host[tail + 2]
@@ -193,5 +240,32 @@ def lesion_wise_scores(pred, truth, label, dilate_iterations=3, dilate_connectiv
         lesions.append(dict(id=j, gt=gt[j], tp=tp[j], pred=touching[j], pred_voxels=vox, dice=dice))
     false_pos = [a for a in range(1, n_pred + 1) if a not in matched]
     denom = len(lesions) + len(false_pos)
-    return dict(lesions=lesions, dropped=dropped, false_positives=false_pos, fp=len(false_pos),
-                lesion_dice=total / denom if denom else 1.0)
+    out = dict(lesions=lesions, dropped=dropped, false_positives=false_pos, fp=len(false_pos),
+               lesion_dice=total / denom if denom else 1.0)
+    if not hd95:
+        return out
+
+    def box(base, i):        # row i - 1 of a component table: zmin, zmax, ymin, ymax, xmin, xmax
+        return host[base + 9 * (i - 1) + 3: base + 9 * (i - 1) + 9]
+
+    tab_p = tail + 4
+    tab_t = tab_p + 9 * capacity
+    scored = [les for les in lesions if les["pred"]]
+    boxes = []
+    for les in scored:
+        bs = [box(tab_t, les["id"])] + [box(tab_p, a) for a in les["pred"]]
+        boxes.append([les["id"]] + [f(b[k] for b in bs) for k, f in enumerate((min, max) * 3)])
+    words = _lesion_surfaces(ids_p, ids_t, g, pairs, host[0], boxes, spacing) if scored else []
+    for les, row in zip(scored, words):
+        if (row[0], row[1]) != (les["gt"], les["pred_voxels"]):
+            raise _lib.HdfError(f"lesion_wise_scores: lesion {les['id']}: its crop holds {row[0]} truth and {row[1]} predicted "
+                                f"voxels, the overlap table {les['gt']} and {les['pred_voxels']}")
+        s = scores_from_result(row) if spacing is None else scores_from_result_mm(row)
+        les.update(surface=row, hd=s["HausdorffDistance"], hd95=s["HausdorffDistance95"])
+    total_hd = 0.0
+    for les in lesions:
+        if not les["pred"]:
+            les.update(surface=None, hd=penalty, hd95=penalty)
+        total_hd += penalty if les["hd95"] != les["hd95"] else les["hd95"]          # (NaN: an invalid pair of masks)
+    out["lesion_hd95"] = (total_hd + penalty * len(false_pos)) / denom if denom else 0.0
+    return out

@@ -441,6 +441,43 @@ int hdf_cc_pairs(const int32_t* ids_a, const int32_t* ids_b, const uint8_t* mask
                  int D, int H, int W, int64_t capacity, int64_t* pairs /* [capacity][4] */, uint64_t* result /* [4] */,
                  void* workspace, int64_t workspace_bytes, hdf_stream stream);
 
+/* ---- per-lesion surface distances: the second number of the BraTS-2023 lesion-wise protocol (the reference has no such
+ * code: its users build two full-volume masks per truth lesion on the host and hand them to SimpleITK or scipy).  For row
+ * i of `lesions`, with truth id j,
+ *   T_i      = the voxels v with truth_mask[v] != 0 and ids_truth[v] == j
+ *   P_i      = the voxels v with ids_pred[v] = a > 0 for which the row (a, j) is among the first n_pairs rows of `pairs`
+ *   results  uint64 [L][12]: row i = the twelve words hdf_surface_distances leaves for the masks (T_i, P_i) over the whole
+ *            volume; with a spacing (host pointer, as hdf_surface_distances_mm takes it; nullable) the twelve words of
+ *            hdf_surface_distances_mm.  Every word is equal to that call's, not close to it.
+ * ids_pred, ids_truth: int32 [D][H][W]; truth_mask: uint8 [D][H][W]; pairs: int64 rows a, b, n, m in ascending (a, b) as
+ * hdf_cc_pairs leaves them (n and m are not read), all on the device.  lesions: HOST int32 [L][7] = j, zmin, zmax, ymin,
+ * ymax, xmin, xmax (inclusive): a box that contains every voxel of T_i and of P_i -- a larger one is as good; one that
+ * misses a voxel gives the distances of what is inside it (words 0 and 1 then fall short of the sizes the caller knows).
+ * The entry grows the box by one voxel on every side, clamps it to the volume, carves both masks of every crop as 0 / 1
+ * bytes into the workspace (one launch per 64 lesions, the rows passed in the kernel arguments: nothing is uploaded, and
+ * `lesions` may be freed on return) and runs the surface entry once per lesion on its crop.  That is exact: every B26
+ * seed, every C6 contour voxel and every 26-neighbour of a mask voxel lies inside the crop; where a side is clamped the
+ * crop's face is the volume's face, where it is not the added layer is true background; and a mask fills the crop only if it
+ * fills the volume.  The cost is that of the summed crop voxels, not of L volumes.
+ *   workspace  hdf_lesion_surface_workspace_bytes(lesions, L, D, H, W, mm) bytes, mm = 1 when a spacing is given and 0 when not
+ *            (neither size covers the other), aligned to 8 bytes.  From byte 0 the crops, packed without padding in row
+ *            order: crop i takes 2 n_i bytes, n_i = its voxels, the mask of T_i in [D'][H'][W'] order first, that of P_i
+ *            behind it -- both can be read back after the call.  Then, on a 256-byte boundary, one scratch area of
+ *            hdf_surface_workspace_bytes / hdf_surface_mm_workspace_bytes of the largest crop, shared by all lesions.
+ *            The size is the contract: crops that do not fit are refused, never processed in parts.
+ * Integer compares and plain stores only (csrc/lesion_surface.hip), then the surface entry's own kernels: two calls agree
+ * in every byte.  The kernels are ordered on `stream`, nothing waits on the host, and the workspace may be reused by the
+ * next call on the same stream without clearing.  L = 0 launches nothing.  Refused (HDF_ERR_ARG, message "surface: ...")
+ * before anything is launched: a spacing hdf_surface_distances_mm refuses, a dimension outside 1..1024, L < 0, n_pairs < 0,
+ * a null required pointer (pairs may be null when n_pairs = 0), a row with j < 1 or with a box that has min > max or leaves
+ * the volume, a workspace below the size function (which returns -1 for refused arguments) or not aligned to 8 bytes,
+ * results or the workspace overlapping each other or an input. */
+int64_t hdf_lesion_surface_workspace_bytes(const int32_t* lesions /* host [L][7] */, int64_t L, int D, int H, int W, int mm);
+int hdf_lesion_surface(const int32_t* ids_pred, const int32_t* ids_truth, const uint8_t* truth_mask, int D, int H, int W,
+                       const int64_t* pairs, int64_t n_pairs, const int32_t* lesions /* host [L][7] */, int64_t L,
+                       const double* spacing /* host, nullable */, void* workspace, int64_t workspace_bytes,
+                       uint64_t* results /* [L][12] */, hdf_stream stream);
+
 /* ---- binary morphology of a label map (the reference has no such code: its users run scipy.ndimage.binary_dilation /
  * binary_erosion / binary_opening / binary_closing / binary_fill_holes on the host).  volume: uint8 [D][H][W] on the device.
  *   input mask   label = 0: every non-zero voxel is foreground; k in 1..255: only the voxels equal to k are.
