@@ -1,18 +1,21 @@
 // The C ABI of the entries on a uint8 / int32 volume [D][H][W]: surface distances and the average surface distance, in
 // voxels and in physical units (surface.hip, surface_asd.hip, surface_mm.hip), connected components (components.hip), the
-// overlap table of two id maps (cc_pairs.hip), per-lesion surface distances on crops (lesion_surface.hip) and binary
-// morphology (morphology.hip).  Every entry checks its arguments on
+// overlap table of two id maps (cc_pairs.hip), per-lesion surface distances on crops (lesion_surface.hip), binary
+// morphology (morphology.hip) and lesion candidates from a probability map (detect.hip).  Every entry checks its arguments on
 // the host -- the first check that fails decides the message, "<family>: <entry>: ..." -- and hands on to the unit's
 // launcher.  Nothing here touches a plan.
+#include <cmath>
+
 #include "../../include/hdf.h"
 #include "cc_pairs.h"
 #include "components.h"
+#include "detect.h"
 #include "lesion_surface.h"
 #include "morphology.h"
 #include "surface.h"
 
 namespace {
-const char SURF[] = "surface", CC[] = "components", MORPH[] = "morphology";
+const char SURF[] = "surface", CC[] = "components", MORPH[] = "morphology", DET[] = "detect";
 
 int check_label(const char* prefix, const char* who, int label, int lo) {
   HDF_CHECK_ARG(label >= lo && label <= 255, "%s: %s: label %d (%d..255)", prefix, who, label, lo);
@@ -311,6 +314,46 @@ int hdf_fill_holes(const uint8_t* volume, int label, int connectivity, int mode,
                               (int64_t)D * H * W));
   return hdf_launch_fill_holes(volume, label, connectivity, mode, D, H, W, out, (unsigned long long*)result, workspace,
                                (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------- lesion candidates
+int64_t hdf_detect_workspace_bytes(int D, int H, int W) {
+  return ws_bytes_or_minus1(DET, "workspace_bytes", D, H, W, hdf_detect_ws_bytes);
+}
+int hdf_detect_candidates(const float* prob, int D, int H, int W, int num_lesions, double factor, double stop, int connectivity,
+                          int remove_adjacent, int64_t min_voxels, int first_round, int rounds, float* detection_map,
+                          int32_t* indexed, int64_t* table, int64_t table_rows, uint64_t* result, void* workspace,
+                          int64_t workspace_bytes, hdf_stream stream) {
+  const char* who = "candidates";
+  HDF_TRY(hdf_vol_check_dims(DET, who, D, H, W));
+  HDF_CHECK_ARG(num_lesions >= 1, "detect: %s: num_lesions %d (at least 1)", who, num_lesions);
+  HDF_CHECK_ARG(std::isfinite(factor) && factor > 1.0, "detect: %s: factor %g (finite, above 1)", who, factor);
+  HDF_CHECK_ARG(std::isfinite(stop) && stop > 0.0, "detect: %s: stop %g (finite, above 0)", who, stop);
+  HDF_CHECK_ARG(connectivity == 6 || connectivity == 18 || connectivity == 26, "detect: %s: connectivity %d (6, 18 or 26)", who,
+                connectivity);
+  HDF_CHECK_ARG(remove_adjacent == 0 || remove_adjacent == 1, "detect: %s: remove_adjacent %d (0 or 1)", who, remove_adjacent);
+  HDF_CHECK_ARG(min_voxels >= 0, "detect: %s: min_voxels %lld is negative", who, (long long)min_voxels);
+  HDF_CHECK_ARG(rounds >= 1 && first_round >= 0 && table_rows >= 0 && table_rows < ((int64_t)1 << 31),
+                "detect: %s: rounds %d, first_round %d, table_rows %lld (rounds >= 1, first_round >= 0, table_rows in 0..2^31-1)",
+                who, rounds, first_round, (long long)table_rows);
+  HDF_TRY(check_nonnull(DET, who, prob && detection_map && indexed && result && (table_rows == 0 || table)));
+  const int64_t need = hdf_detect_ws_bytes(D, H, W), V = (int64_t)D * H * W;
+  HDF_TRY(check_workspace(DET, who, workspace, workspace_bytes, need));
+  HDF_TRY(check_aligned8(DET, who, "table", table));
+  HDF_TRY(check_aligned8(DET, who, "result", result));
+  const struct { const void* p; int64_t n; const char* name; } buf[6] = {
+      {prob, V * 4, "prob"},     {detection_map, V * 4, "detection_map"}, {indexed, V * 4, "indexed"},
+      {table, table_rows * HDF_DETECT_TABLE_COLS * 8, "table"}, {result, 32, "result"}, {workspace, need, "workspace"}};
+  for (int i = 0; i < 6; i++)
+    for (int j = i + 1; j < 6; j++)
+      HDF_CHECK_ARG(buf[i].n == 0 || buf[j].n == 0 || !hdf_overlap(buf[i].p, buf[i].n, buf[j].p, buf[j].n),
+                    "detect: %s: %s overlaps %s", who, buf[i].name, buf[j].name);
+  DetectArgs args;
+  args.num_lesions = num_lesions, args.connectivity = connectivity, args.remove_adjacent = remove_adjacent;
+  args.first_round = first_round, args.rounds = rounds, args.factor = factor, args.stop = stop;
+  args.min_voxels = min_voxels, args.table_rows = table_rows;
+  return hdf_launch_detect(prob, D, H, W, args, detection_map, indexed, (long long*)table, (unsigned long long*)result,
+                           workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ _COMPONENTS = ("connected_components", "component_table", "component_stats", "ke
 _MORPHOLOGY = ("binary_dilation", "binary_erosion", "binary_opening", "binary_closing", "binary_fill_holes", "morph_class",
                "fill_class_holes")
 _LESIONS = ("component_overlap", "match_components", "lesion_wise_scores")
+_DETECTION = ("extract_lesion_candidates", "match_candidates", "DetectionEvaluator")
 _INFERENCE = ("cal_steps", "gaussian_tables", "sliding_window_predict", "slice_predict")
 
 
@@ -34,9 +35,12 @@ def __getattr__(name):
     if name in _LESIONS:
         from . import lesions
         return getattr(lesions, name)
+    if name in _DETECTION:
+        from . import detection
+        return getattr(detection, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def __dir__():
     return sorted(list(globals()) + list(_AUGMENT) + list(_SURFACE) + list(_COMPONENTS) + list(_MORPHOLOGY) +
-                  list(_LESIONS) + list(_INFERENCE))
+                  list(_LESIONS) + list(_DETECTION) + list(_INFERENCE))

@@ -87,6 +87,9 @@ _PROTOS = {
     "hdf_morph": (_i, [_vp] + [_i] * 9 + [_vp, _vp, _vp, _i64, _vp]),
     "hdf_fill_holes_workspace_bytes": (_i64, [_i, _i, _i]),
     "hdf_fill_holes": (_i, [_vp] + [_i] * 6 + [_vp, _vp, _vp, _i64, _vp]),
+    "hdf_detect_workspace_bytes": (_i64, [_i, _i, _i]),
+    "hdf_detect_candidates": (_i, [_vp, _i, _i, _i, _i, C.c_double, C.c_double, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _i64, _vp,
+                                   _vp, _i64, _vp]),
     "hdf_normalize_workspace_bytes": (_i64, [_i]),
     "hdf_normalize_mr": (_i, [_vp, _i, _i64, _vp, _vp]),
     "hdf_normalize_petct": (_i, [_vp, _i, _i64, _f, _f, _vp, _vp]),

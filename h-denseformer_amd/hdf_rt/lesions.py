@@ -88,6 +88,30 @@ def overlap_value(n, size_a, size_b, overlap):
     return n / (size_a + size_b - n)          # 'iou', and the order under 'any'
 
 
+def _match_rows(rows, n_pred, n_truth, min_overlap, overlap):
+    """The host half of the detection matching, shared by match_components and detection.match_candidates: from the rows
+    (a, b, n, m) of an overlap table with both zero flags, the sizes, the candidate pairs and the greedy one-to-one
+    assignment.  The result dict of match_components with confidence = None."""
+    size_p, size_t = [0] * (n_pred + 1), [0] * (n_truth + 1)
+    for a, b, n, _m in rows:
+        size_p[a] += n
+        size_t[b] += n
+    cand = []
+    for a, b, n, _m in rows:
+        if a > 0 and b > 0:
+            ov = overlap_value(n, size_p[a], size_t[b], overlap)
+            if overlap == "any" or ov >= min_overlap:
+                cand.append((-ov, b, a))
+    cand.sort()
+    pred_match, truth_match = [(0, 0.0)] * n_pred, [(0, 0.0)] * n_truth
+    for neg, b, a in cand:
+        if pred_match[a - 1][0] == 0 and truth_match[b - 1][0] == 0:
+            pred_match[a - 1], truth_match[b - 1] = (b, -neg), (a, -neg)
+    tp = sum(1 for t, _ in pred_match if t)
+    return dict(tp=tp, fp=n_pred - tp, fn=n_truth - tp, truth_match=truth_match, pred_match=pred_match, pred_size=size_p[1:],
+                truth_size=size_t[1:], confidence=None)
+
+
 def match_components(pred, truth, connectivity=26, pred_label=0, truth_label=0, score=None, min_overlap=0.1, overlap="iou",
                      capacity=4096):
     """Detection matching of the components of `pred` (predicted lesions) with those of `truth`, both uint8 / bool maps:
@@ -123,27 +147,12 @@ def match_components(pred, truth, connectivity=26, pred_label=0, truth_label=0, 
     rows = _rows(host, "match_components", capacity)
     tail = 4 + 4 * capacity
     n_pred, n_truth = host[tail], host[tail + 2]
-    size_p, size_t = [0] * (n_pred + 1), [0] * (n_truth + 1)
-    for a, b, n, _m in rows:
-        size_p[a] += n
-        size_t[b] += n
-    cand = []
-    for a, b, n, _m in rows:
-        if a > 0 and b > 0:
-            ov = overlap_value(n, size_p[a], size_t[b], overlap)
-            if overlap == "any" or ov >= min_overlap:
-                cand.append((-ov, b, a))
-    cand.sort()
-    pred_match, truth_match = [(0, 0.0)] * n_pred, [(0, 0.0)] * n_truth
-    for neg, b, a in cand:
-        if pred_match[a - 1][0] == 0 and truth_match[b - 1][0] == 0:
-            pred_match[a - 1], truth_match[b - 1] = (b, -neg), (a, -neg)
-    tp = sum(1 for t, _ in pred_match if t)
+    out = _match_rows(rows, n_pred, n_truth, min_overlap, overlap)
     conf = None
     if score is not None:
         conf = [struct.unpack("<f", struct.pack("<i", w))[0] for w in host[tail + 4: tail + 4 + n_pred]]
-    return dict(tp=tp, fp=n_pred - tp, fn=n_truth - tp, truth_match=truth_match, pred_match=pred_match, pred_size=size_p[1:],
-                truth_size=size_t[1:], confidence=conf)
+    out["confidence"] = conf
+    return out
 
 
 def _lesion_surfaces(ids_p, ids_t, g, pairs, n_pairs, boxes, spacing):

@@ -525,6 +525,47 @@ int64_t hdf_fill_holes_workspace_bytes(int D, int H, int W);
 int hdf_fill_holes(const uint8_t* volume, int label, int connectivity, int mode, int D, int H, int W, uint8_t* out,
                    uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream);
 
+/* ---- lesion candidates from a probability map: the "dynamic" lesion extraction of detection evaluation (peak, threshold
+ * at peak / factor, the component of the peak, drop what touches an accepted candidate, num_lesions lesions).  The reference
+ * has no such code: its users copy the fp32 map to the host and run scipy.ndimage.label once per round.  prob: fp32
+ * [D][H][W] on the device.  This text is the contract; it claims equality with no package.
+ *   setup      w = prob where 0 < prob <= FLT_MAX, else 0 (NaN, negative, -0 and inf become 0); detection_map = 0 (fp32),
+ *            indexed = 0 (int32), kept = 0, the table all zeros.
+ *   one round  1. kept == num_lesions: finished, reason 1 (count).
+ *            2. m = max(w), a = the smallest linear index with w[a] == m; (double)m < stop: finished, reason 2 (stop).
+ *            3. thr = (double)m / factor, one fp64 division; the mask is (double)w[v] > thr (a is in it: factor > 1, m > 0).
+ *            4. the mask labelled under `connectivity` (hdf_cc_label's kernels); cur = the component of a, size = |cur|.
+ *            5. touch = some voxel of cur has a voxel with indexed > 0 in its 3x3x3 neighbourhood, itself included,
+ *               clipped at the faces -- always the 26-neighbourhood, whatever `connectivity` is.
+ *            6. status 1 (adjacent) if remove_adjacent and touch; else 2 (small) if size < min_voxels; else 0 (kept):
+ *               kept += 1, detection_map = m and indexed = kept over cur.
+ *            7. w = 0 over cur whatever the status; table row `round` = index (kept, or 0 for a dropped candidate), the
+ *               bits of m, size, a, status, the fp64 bits of thr; round += 1.
+ *            A dropped candidate takes no index and does not count towards num_lesions; it still leaves w, which is what
+ *            ends the loop.  A finished call changes nothing in later rounds.
+ *   rounds     the call runs `rounds` rounds.  first_round == 0 starts from the setup; first_round == k > 0 continues the
+ *            state that the previous call left in the same workspace, detection_map, indexed and table, and must equal the
+ *            rounds run so far -- where it does not (or the workspace holds no state) nothing is changed and result[2] is 3.
+ *            This is a check on the device, not on the host.  The other arguments must be those of the first call.
+ *   table      int64 [table_rows][6], one row per round run; a round past table_rows leaves no row and is counted instead.
+ *   result     [4] uint64 = the rounds run so far (over all calls), kept, finished (0 running, 1 count, 2 stop, 3 a
+ *            first_round that does not fit), the rows dropped for table_rows.
+ * The peak is the maximum over (bits of w << 32 | 0xFFFFFFFF - index), one 64-bit integer atomicMax per workgroup:
+ * non-negative floats order as their bits, so m, a and the first-index tie rule are exact.  Integer atomics only; every
+ * output is exact and the same from call to call.  No kernel waits on another workgroup (csrc/detect.hip).  All pointers
+ * are device memory, the kernels are ordered on `stream` and nothing waits on the host.  Refused (HDF_ERR_ARG, message
+ * "detect: ...") before anything is launched: a dimension outside 1..1024, D*H*W >= 2^31, num_lesions < 1, factor <= 1 or
+ * not finite, stop <= 0 or not finite, connectivity not 6 / 18 / 26, remove_adjacent not 0 / 1, min_voxels < 0, rounds < 1,
+ * first_round < 0, table_rows < 0, a null required pointer (table may be null when table_rows = 0), a workspace below
+ * hdf_detect_workspace_bytes(D, H, W) (w, the mask, the ids, 256 bytes of state and hdf_cc_workspace_bytes, about 14 bytes
+ * a voxel; -1 for refused dimensions) or not aligned to 8 bytes, any of prob, detection_map, indexed, table, result and
+ * the workspace overlapping another. */
+int64_t hdf_detect_workspace_bytes(int D, int H, int W);
+int hdf_detect_candidates(const float* prob, int D, int H, int W, int num_lesions, double factor, double stop,
+                          int connectivity, int remove_adjacent, int64_t min_voxels, int first_round, int rounds,
+                          float* detection_map, int32_t* indexed, int64_t* table /* [table_rows][6] */, int64_t table_rows,
+                          uint64_t* result /* [4] */, void* workspace, int64_t workspace_bytes, hdf_stream stream);
+
 /* ---- input normalisation on the device, in place on one fp32 sample [channels][voxels] -----------------------
  * hdf_normalize_mr: MRNormalize (data_utils/data_loader.py:39-50): every channel divided by its maximum when that is
  * non-zero, then negatives clamped to 0.  hdf_normalize_petct: PETandCTNormalize (:53-68): channel 0 ->

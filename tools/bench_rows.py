@@ -9,6 +9,7 @@ bounded host-side restatement of what the reference does for the same call (nump
   python tools/bench_rows.py components                         (the connected-component rows alone)
   python tools/bench_rows.py morphology                         (the binary morphology rows alone)
   python tools/bench_rows.py lesions                            (the lesion-wise matching rows alone)
+  python tools/bench_rows.py detect                             (the lesion-candidate rows alone)
   python tools/bench_rows.py slice2d                            (the slice-wise 2-D inference row alone)
 """
 import json
@@ -403,6 +404,81 @@ def lesions_row(shapes=((144, 144, 144), (448, 512, 512))):
         torch.cuda.empty_cache()
 
 
+def detect_row(shapes=((24, 384, 384), (160, 160, 160))):
+    """hdf_rt.extract_lesion_candidates (defaults: five lesions, peak / 2.5, connectivity 6, remove_adjacent, chunks of
+    eight rounds) on a blob-like fp32 probability map resident on the device -- a smoothed 1/8-resolution noise field cut at
+    its 93rd percentile, interpolated up, with 0.5 % noise voxels -- as wall time around the call (median of 5; it ends in
+    its own D2H copies), and one hdf_detect_candidates call of eight rounds by HIP events (median of 10 after 3): the first
+    rounds extract, the rest run on an empty mask.  The yardstick of the same run: the map copied to the host and the loop
+    with scipy.ndimage.label / binary_dilation a user writes today, one run, one host thread; its table must equal the
+    device's in every word."""
+    from hdf_rt import detection
+    from hdf_rt._lib import check, lib, ptr, stream_ptr
+    from scipy import ndimage as ndi
+    for shape in shapes:
+        rng = np.random.default_rng(23)
+        low = tuple(max(s // 8, 2) for s in shape)
+        f = ndi.gaussian_filter(rng.random(low), 1.5, mode="nearest")
+        f = np.clip((f - np.quantile(f, 0.93)) / (f.max() - np.quantile(f, 0.93)), 0.0, 1.0)
+        p = (0.9 * ndi.zoom(f, [s / l for s, l in zip(shape, low)], order=1)).astype(np.float32)
+        assert p.shape == shape
+        noise = rng.random(shape) < 0.005
+        p[noise] = rng.uniform(0.0, 0.3, int(noise.sum())).astype(np.float32)
+        dp = torch.from_numpy(p).to(DEV)
+        V = dp.numel()
+
+        def host_path():
+            w = dp.cpu().numpy().copy()
+            idx, kept, rows = np.zeros(shape, np.int32), 0, []
+            while kept < 5:
+                a = int(np.argmax(w))
+                m = w.reshape(-1)[a]
+                if float(m) < 0.01:
+                    break
+                thr = float(m) / 2.5
+                labels, _ = ndi.label(w.astype(np.float64) > thr)
+                cur = labels == labels.reshape(-1)[a]
+                status = 1 if (ndi.binary_dilation(idx > 0, np.ones((3, 3, 3), bool)) & cur).any() else 0
+                if status == 0:
+                    kept += 1
+                    idx[cur] = kept
+                w[cur] = 0
+                rows.append([kept if status == 0 else 0, int(np.float32(m).view(np.uint32)), int(cur.sum()), a, status,
+                             int(np.float64(thr).view(np.int64))])
+            return rows
+
+        def wall(fn, reps):
+            fn()
+            ts = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                fn()
+                ts.append(time.perf_counter() - t)
+            return sorted(ts)[len(ts) // 2]
+
+        t = time.perf_counter()
+        rows = host_path()
+        host_s = time.perf_counter() - t
+        got = detection._extract(dp, 5, 2.5, 0.01, 6, True, 0, 256, 8)
+        ms_call = 1e3 * wall(lambda: detection.extract_lesion_candidates(dp), 5)
+        ws = torch.empty(lib().hdf_detect_workspace_bytes(*shape), dtype=torch.uint8, device=DEV)
+        det, idx = torch.empty(shape, dtype=torch.float32, device=DEV), torch.empty(shape, dtype=torch.int32, device=DEV)
+        table, res = torch.empty((256, 6), dtype=torch.int64, device=DEV), torch.empty(4, dtype=torch.int64, device=DEV)
+        st = stream_ptr()
+        ms_chunk = gpu_ms(lambda: check(lib().hdf_detect_candidates(ptr(dp), *shape, 5, 2.5, 0.01, 6, 1, 0, 0, 8, ptr(det), ptr(idx),
+                                                                    ptr(table), 256, ptr(res), ptr(ws), ws.numel(), st),
+                                        "hdf_detect_candidates"))
+        emit(row="detect", config=f"{shape[0]}x{shape[1]}x{shape[2]} fp32 map, 5 lesions, factor 2.5, connectivity 6, sync_every 8",
+             voxels=V, rounds=got[3][0], kept=got[3][1], finished=got[3][2], d2h_copies=got[4], tables_equal=got[2] == rows,
+             extract_lesion_candidates_ms=ms_call, one_call_of_8_rounds_ms=ms_chunk, rounds_in_that_call=res.cpu().tolist()[0],
+             cpu_baseline={"kind": "port", "what": "D2H copy of the fp32 map + the scipy.ndimage.label / binary_dilation loop",
+                           "s_per_volume": host_s, "threads": 1})
+        del dp, ws, det, idx
+        detection.clear_workspaces()
+        torch.cuda.empty_cache()
+
+
 def slice2d_row(C=3, D=24, S=384, slice_batch=24):
     """slice_predict of HDenseFormer_2D_32(3, 2, (384, 384), 24) on a 3 x 24 x 384^2 volume (the reference's 2-D workload,
     config.py:69-77; bf16, one in-plane window, no mirroring: one hdf_plane_max, one hdf_slice_gather, one forward of 24
@@ -470,6 +546,9 @@ if sys.argv[1:] == ["morphology"]:
     sys.exit(0)
 if sys.argv[1:] == ["lesions"]:
     lesions_row()
+    sys.exit(0)
+if sys.argv[1:] == ["detect"]:
+    detect_row()
     sys.exit(0)
 if sys.argv[1:] == ["resize3d"]:
     resize3d_row()
