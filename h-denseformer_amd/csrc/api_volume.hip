@@ -1,7 +1,8 @@
 // The C ABI of the entries on a uint8 / int32 volume [D][H][W]: surface distances and the average surface distance, in
 // voxels and in physical units (surface.hip, surface_asd.hip, surface_mm.hip), connected components (components.hip), the
 // overlap table of two id maps (cc_pairs.hip), per-lesion surface distances on crops (lesion_surface.hip), binary
-// morphology (morphology.hip) and lesion candidates from a probability map (detect.hip).  Every entry checks its arguments on
+// morphology (morphology.hip), lesion candidates from a probability map (detect.hip) and the measurements of an image
+// under an id map (measure.hip).  Every entry checks its arguments on
 // the host -- the first check that fails decides the message, "<family>: <entry>: ..." -- and hands on to the unit's
 // launcher.  Nothing here touches a plan.
 #include <cmath>
@@ -11,6 +12,7 @@
 #include "components.h"
 #include "detect.h"
 #include "lesion_surface.h"
+#include "measure.h"
 #include "morphology.h"
 #include "surface.h"
 
@@ -244,6 +246,45 @@ int hdf_cc_pairs(const int32_t* ids_a, const int32_t* ids_b, const uint8_t* mask
   }
   return hdf_launch_cc_pairs(ids_a, ids_b, mask, flags, D, H, W, capacity, (long long*)pairs, (unsigned long long*)result,
                              workspace, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------- measurements under an id map
+int64_t hdf_cc_measure_workspace_bytes(int C, int64_t capacity) {
+  if (C < 1 || C > HDF_MEASURE_MAX_CHANNELS || capacity < 1 || capacity > HDF_MEASURE_MAX_CAPACITY) {
+    hdf_set_error("components: measure: C = %d (1..%d), capacity %lld (1..%lld)", C, HDF_MEASURE_MAX_CHANNELS,
+                  (long long)capacity, (long long)HDF_MEASURE_MAX_CAPACITY);
+    return -1;
+  }
+  return hdf_cc_measure_ws_bytes(C, capacity);
+}
+int hdf_cc_measure(const int32_t* ids, const float* image, int C, int D, int H, int W, int64_t capacity, int64_t* geom,
+                   double* stats, int64_t* pos, uint64_t* result, void* workspace, int64_t workspace_bytes, hdf_stream stream) {
+  const char* who = "measure";
+  HDF_CHECK_ARG(C >= 1 && C <= HDF_MEASURE_MAX_CHANNELS, "components: %s: C = %d (1..%d)", who, C, HDF_MEASURE_MAX_CHANNELS);
+  HDF_TRY(hdf_vol_check_dims(CC, who, D, H, W));
+  HDF_CHECK_ARG(capacity >= 1 && capacity <= HDF_MEASURE_MAX_CAPACITY, "components: %s: capacity %lld (1..%lld)", who,
+                (long long)capacity, (long long)HDF_MEASURE_MAX_CAPACITY);
+  HDF_TRY(check_nonnull(CC, who, ids && image && geom && stats && pos && result));
+  const int64_t need = hdf_cc_measure_ws_bytes(C, capacity), V = (int64_t)D * H * W;
+  HDF_TRY(check_workspace(CC, who, workspace, workspace_bytes, need));
+  HDF_TRY(check_aligned8(CC, who, "geom", geom));
+  HDF_TRY(check_aligned8(CC, who, "stats", stats));
+  HDF_TRY(check_aligned8(CC, who, "pos", pos));
+  HDF_TRY(check_aligned8(CC, who, "result", result));
+  const struct { const void* p; int64_t n; const char* name; } out[5] = {{geom, capacity * 32, "geom"},
+                                                                        {stats, C * capacity * 64, "stats"},
+                                                                        {pos, C * capacity * 16, "pos"},
+                                                                        {result, 32, "result"},
+                                                                        {workspace, need, "workspace"}};
+  for (int i = 0; i < 5; i++) {
+    HDF_CHECK_ARG(!hdf_overlap(out[i].p, out[i].n, ids, V * 4) && !hdf_overlap(out[i].p, out[i].n, image, C * V * 4),
+                  "components: %s: %s overlaps an input", who, out[i].name);
+    for (int j = i + 1; j < 5; j++)
+      HDF_CHECK_ARG(!hdf_overlap(out[i].p, out[i].n, out[j].p, out[j].n), "components: %s: %s overlaps %s", who, out[i].name,
+                    out[j].name);
+  }
+  return hdf_launch_cc_measure(ids, image, C, D, H, W, capacity, (long long*)geom, stats, (long long*)pos,
+                               (unsigned long long*)result, workspace, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------- per-lesion surface distances

@@ -20,6 +20,8 @@
 
 #include <algorithm>
 
+#include "cc_runs.h"
+
 namespace {
 constexpr int CHUNK = 1024;   // voxels per workgroup in the three passes that rank the roots: four consecutive ones a thread
 
@@ -221,17 +223,6 @@ __global__ __launch_bounds__(256) void cc_ids_kernel(const int32_t* __restrict__
   }
 }
 
-// ------------------------------------------------------------------------------------------------ runs
-// The lanes of a wave hold 64 consecutive voxels.  A run is a maximal stretch of lanes with the same non-zero id that
-// does not cross a row start: its first lane (the head) speaks for all of it, one set of atomics instead of `len`.
-// Returns the distance from this lane to the end of its stretch (for a head: the run's length).
-__device__ __forceinline__ int wave_run(int id, bool row_start, bool* head) {
-  const int lane = threadIdx.x & 63;
-  const int prev = __shfl_up(id, 1, 64);
-  *head = id > 0 && (lane == 0 || prev != id || row_start);
-  return wave_run_len(__ballot(*head || id <= 0), lane);
-}
-
 // ------------------------------------------------------------------------------------------------ table
 constexpr long long NONE = 0x7fffffffffffffffll;
 __device__ __forceinline__ bool is_min_col(int c) { return c == 2 || c == 3 || c == 5 || c == 7; }
@@ -245,29 +236,7 @@ __global__ __launch_bounds__(256) void cc_table_init_kernel(long long* __restric
   }
 }
 
-#define CC_MIN(p, x) __hip_atomic_fetch_min((p), (long long)(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define CC_MAX(p, x) __hip_atomic_fetch_max((p), (long long)(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define CC_ADD(p, x) __hip_atomic_fetch_add((p), (x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
-// Runs of one component arrive by the thousand at the same table row (a tumour is one component of millions of voxels), and
-// atomics on one address are served one at a time.  A workgroup therefore walks SPAN consecutive voxels and collects its
-// runs in LDS first: SLOTS slots, slot id % SLOTS claimed by the first id that asks (compare-and-swap on the slot's id); a
-// run whose slot belongs to another id goes to memory directly.  The slots are flushed once per workgroup.  Sums, minima
-// and maxima of integers: the grouping changes no result.  HDF_CC_NO_LDS_SLOTS: A/B builds, every run straight to memory.
-constexpr int SLOTS = 64, SPAN_TRIPS = 32, SPAN = 256 * SPAN_TRIPS;
-__device__ __forceinline__ bool claim_slot(int* slot_id, int id) {
-#ifdef HDF_CC_NO_LDS_SLOTS
-  return false;
-#else
-  int owner = __hip_atomic_load(slot_id + (id & (SLOTS - 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  if (owner == 0) {
-    owner = atomicCAS(slot_id + (id & (SLOTS - 1)), 0, id);
-    if (owner == 0) owner = id;
-  }
-  return owner == id;
-#endif
-}
-
+// (the runs of a wave, the LDS slots of a workgroup and the atomics on a row: cc_runs.h)
 __device__ __forceinline__ void table_to_memory(long long* __restrict__ table, int* __restrict__ smax, int id, int len, int val,
                                                 int first, int z0, int z1, int y0, int y1, int x0, int x1, int key) {
   long long* row = table + (int64_t)(id - 1) * HDF_CC_TABLE_COLS;

@@ -12,6 +12,7 @@ _MORPHOLOGY = ("binary_dilation", "binary_erosion", "binary_opening", "binary_cl
                "fill_class_holes")
 _LESIONS = ("component_overlap", "match_components", "lesion_wise_scores")
 _DETECTION = ("extract_lesion_candidates", "match_candidates", "DetectionEvaluator")
+_REGIONS = ("region_measure", "region_stats", "pet_lesion_measures")
 _INFERENCE = ("cal_steps", "gaussian_tables", "sliding_window_predict", "slice_predict")
 
 
@@ -38,9 +39,12 @@ def __getattr__(name):
     if name in _DETECTION:
         from . import detection
         return getattr(detection, name)
+    if name in _REGIONS:
+        from . import regions
+        return getattr(regions, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def __dir__():
     return sorted(list(globals()) + list(_AUGMENT) + list(_SURFACE) + list(_COMPONENTS) + list(_MORPHOLOGY) +
-                  list(_LESIONS) + list(_DETECTION) + list(_INFERENCE))
+                  list(_LESIONS) + list(_DETECTION) + list(_REGIONS) + list(_INFERENCE))

@@ -441,6 +441,48 @@ int hdf_cc_pairs(const int32_t* ids_a, const int32_t* ids_b, const uint8_t* mask
                  int D, int H, int W, int64_t capacity, int64_t* pairs /* [capacity][4] */, uint64_t* result /* [4] */,
                  void* workspace, int64_t workspace_bytes, hdf_stream stream);
 
+/* ---- measurements of an image under an id map: what scipy.ndimage's sum_labels, mean, variance / standard_deviation,
+ * minimum / maximum, minimum_position / maximum_position and center_of_mass give, one call per statistic and channel, on
+ * the host (the reference has no such code).  ids: int32 [D][H][W], image: fp32 [C][D][H][W], both on the device.  Any
+ * non-negative numbering is valid -- the ids of hdf_cc_label, the index map of hdf_detect_candidates, a class map widened to
+ * int32; a value below 0 counts as 0, and ids above `capacity` are left out of everything but result[0] and result[1].
+ * With z, y, x the coordinates of a voxel, x_v its value in channel c, and the sums running over the voxels of id:
+ *   geom     int64 [capacity][4], row id-1 = n, sum z, sum y, sum x: exact integers.
+ *   stats    fp64 [C][capacity][8], row id-1 of channel c = S1 = sum x_v, mean = S1 / n, M2 = sum (x_v - mean)^2, min, max,
+ *            Wz = sum z x_v, Wy = sum y x_v, Wx = sum x x_v.  The variance scipy reports is M2 / n, its centre of mass W / S1.
+ *   pos      int64 [C][capacity][2], row id-1 of channel c = the linear voxel index of the minimum and of the maximum; on a
+ *            tie the SMALLEST index for both -- np.argmin / np.argmax and the peak of hdf_detect_candidates, not scipy,
+ *            whose maximum_position returns the last one.
+ *   result   [4] uint64 = the largest id met (capacity or not), the voxels with id > 0, the voxels with id in 1..capacity, 0.
+ * A row whose id no voxel holds is all zero bytes in every output.  A -0 counts as +0 (min and max never return -0, and a sum that is zero is +0).  A NaN
+ * or an infinity in a component is the caller's error: that component's fp64 outputs are unspecified, no other row
+ * changes, nothing faults (no address is formed from a value of the image).
+ * The numerical contract.  n, the coordinate sums, min, max, pos and result are exact: integer atomics, for the extrema
+ * on the 64-bit keys (order(x) << 32 | ~index) and (~order(x) << 32 | ~index), order() mapping a float's bits to an
+ * unsigned that orders like its value -- negative values included.  The fp64 sums use no floating-point atomic, and every
+ * term is exact in fp64 (x_v; z x_v with 10 + 24 bits; x_v - mean is rounded once and squared inside a fused multiply-add),
+ * so only the order of the additions is free, and it is fixed (csrc/measure.hip): the box of the id (exact) is cut, in its
+ * own linear order, into HDF_MEASURE_SLABS = 8 contiguous slabs of ceil(box voxels / 8); one workgroup of 256 threads per
+ * slab, thread t adding the voxels t, t + 256, ... of the slab that hold the id, in that order, from 0; the 256 sums joined by
+ * the tree of block_sum_f64 (xor shuffles over 32, 16, ..., 1 lanes, then (w0 + w1) + (w2 + w3)); the eight slabs added in
+ * index order.  M2 is a second such pass with the finished mean.  Hence the fp64 outputs of a row are the same in every
+ * bit from call to call, whatever the workspace held before, and for every capacity >= the row's id.  Against the
+ * exactly rounded sums they stay within n u sum|t| for a sum of n exact terms t (u = 2^-53), that / n + u |mean| for the
+ * mean, and 2 [(n + 2) u M2 + n ((n + 1) u sum|x| / n)^2] for M2 (tests/measure_ref.py derives them).
+ * The work: one pass over the id map that reads the image where an id counts, then two passes whose cost is the summed
+ * voxels of the boxes (times C), not the volume -- as hdf_lesion_surface pays for its crops; a thin diagonal component
+ * pays for its whole box.  No kernel waits on another workgroup and every loop is bounded by the volume.  All pointers
+ * are device memory, the kernels are ordered on `stream`, nothing waits on the host, and a workspace may be reused by the
+ * next call on the same stream without clearing.  Refused (HDF_ERR_ARG, message "components: measure: ...") before
+ * anything is launched: C outside 1..8, a dimension outside 1..1024, capacity outside 1..65536, a null pointer, a
+ * workspace below hdf_cc_measure_workspace_bytes(C, capacity) (24 bytes an id for the boxes, 16 C for the keys, 256 C for
+ * the partial sums; -1 for a refused C or capacity) or not aligned to 8 bytes, geom, stats, pos or result not aligned to 8
+ * bytes, any output or the workspace overlapping an input or each other. */
+int64_t hdf_cc_measure_workspace_bytes(int C, int64_t capacity);
+int hdf_cc_measure(const int32_t* ids, const float* image /* [C][D][H][W] */, int C, int D, int H, int W, int64_t capacity,
+                   int64_t* geom /* [capacity][4] */, double* stats /* [C][capacity][8] */, int64_t* pos /* [C][capacity][2] */,
+                   uint64_t* result /* [4] */, void* workspace, int64_t workspace_bytes, hdf_stream stream);
+
 /* ---- per-lesion surface distances: the second number of the BraTS-2023 lesion-wise protocol (the reference has no such
  * code: its users build two full-volume masks per truth lesion on the host and hand them to SimpleITK or scipy).  For row
  * i of `lesions`, with truth id j,
