@@ -11,7 +11,7 @@ SRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib")
 OBJ = os.path.join(HERE, "build")
 SOURCES = ["conv_igemm.hip", "conv_wgrad.hip", "conv_wgrad2.hip", "conv_wgrad_s2.hip", "conv_s2.hip", "conv_pack.hip", "conv_wr.hip", "conv_first.hip", "norm_ops.hip", "pool_ops.hip", "head_ops.hip", "transformer.hip", "transformer_fused.hip", "tf_chain_fwd.hip", "tf_chain_bwd.hip", "tf_chain_host.hip", "loss.hip", "loss_topk.hip",
-           "metrics.hip", "sw_infer.hip", "slice_infer.hip", "surface.hip", "surface_asd.hip", "surface_mm.hip", "components.hip", "cc_pairs.hip", "lesion_surface.hip", "morphology.hip", "detect.hip", "measure.hip", "augment.hip", "resize.hip", "optim.hip", "plan.hip", "embed2d.hip", "exec.hip", "exec_tf.hip", "api_ops.hip", "api_volume.hip"]
+           "metrics.hip", "sw_infer.hip", "slice_infer.hip", "surface.hip", "surface_asd.hip", "surface_mm.hip", "components.hip", "cc_pairs.hip", "lesion_surface.hip", "morphology.hip", "detect.hip", "measure.hip", "quantiles.hip", "augment.hip", "resize.hip", "optim.hip", "plan.hip", "embed2d.hip", "exec.hip", "exec_tf.hip", "api_ops.hip", "api_volume.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # per-file additions.  conv_wr.hip: MFMA results in architectural VGPRs -- its AGPR half holds the 216 weight registers
 # of a wave (left to its heuristic hipcc puts the accumulators there and spills weights to scratch); its tile phase is one

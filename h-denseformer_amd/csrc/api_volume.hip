@@ -1,8 +1,8 @@
 // The C ABI of the entries on a uint8 / int32 volume [D][H][W]: surface distances and the average surface distance, in
 // voxels and in physical units (surface.hip, surface_asd.hip, surface_mm.hip), connected components (components.hip), the
 // overlap table of two id maps (cc_pairs.hip), per-lesion surface distances on crops (lesion_surface.hip), binary
-// morphology (morphology.hip), lesion candidates from a probability map (detect.hip) and the measurements of an image
-// under an id map (measure.hip).  Every entry checks its arguments on
+// morphology (morphology.hip), lesion candidates from a probability map (detect.hip), the measurements of an image
+// under an id map (measure.hip) and its order statistics (quantiles.hip).  Every entry checks its arguments on
 // the host -- the first check that fails decides the message, "<family>: <entry>: ..." -- and hands on to the unit's
 // launcher.  Nothing here touches a plan.
 #include <cmath>
@@ -14,6 +14,7 @@
 #include "lesion_surface.h"
 #include "measure.h"
 #include "morphology.h"
+#include "quantiles.h"
 #include "surface.h"
 
 namespace {
@@ -285,6 +286,49 @@ int hdf_cc_measure(const int32_t* ids, const float* image, int C, int D, int H, 
   }
   return hdf_launch_cc_measure(ids, image, C, D, H, W, capacity, (long long*)geom, stats, (long long*)pos,
                                (unsigned long long*)result, workspace, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------- order statistics under an id map
+// q is a host pointer: checked, and read, before anything is launched.
+int64_t hdf_cc_quantiles_workspace_bytes(int C, int64_t capacity, int Q) {
+  if (C < 1 || C > HDF_MEASURE_MAX_CHANNELS || capacity < 1 || capacity > HDF_MEASURE_MAX_CAPACITY || Q < 1 ||
+      Q > HDF_QUANTILES_MAX_LEVELS) {
+    hdf_set_error("components: quantiles: C = %d (1..%d), capacity %lld (1..%lld), Q = %d (1..%d)", C, HDF_MEASURE_MAX_CHANNELS,
+                  (long long)capacity, (long long)HDF_MEASURE_MAX_CAPACITY, Q, HDF_QUANTILES_MAX_LEVELS);
+    return -1;
+  }
+  return hdf_cc_quantiles_ws_bytes(capacity);
+}
+int hdf_cc_quantiles(const int32_t* ids, const float* image, int C, int D, int H, int W, int64_t capacity, const double* q, int Q,
+                     int64_t* count, double* values, uint64_t* result, void* workspace, int64_t workspace_bytes,
+                     hdf_stream stream) {
+  const char* who = "quantiles";
+  HDF_CHECK_ARG(C >= 1 && C <= HDF_MEASURE_MAX_CHANNELS, "components: %s: C = %d (1..%d)", who, C, HDF_MEASURE_MAX_CHANNELS);
+  HDF_TRY(hdf_vol_check_dims(CC, who, D, H, W));
+  HDF_CHECK_ARG(capacity >= 1 && capacity <= HDF_MEASURE_MAX_CAPACITY, "components: %s: capacity %lld (1..%lld)", who,
+                (long long)capacity, (long long)HDF_MEASURE_MAX_CAPACITY);
+  HDF_CHECK_ARG(Q >= 1 && Q <= HDF_QUANTILES_MAX_LEVELS, "components: %s: Q = %d (1..%d)", who, Q, HDF_QUANTILES_MAX_LEVELS);
+  HDF_TRY(check_nonnull(CC, who, ids && image && q && count && values && result));
+  for (int i = 0; i < Q; i++)   // (a NaN fails both comparisons)
+    HDF_CHECK_ARG(q[i] >= 0.0 && q[i] <= 1.0, "components: %s: level %d is %g (0..1)", who, i, q[i]);
+  const int64_t need = hdf_cc_quantiles_ws_bytes(capacity), V = (int64_t)D * H * W;
+  HDF_TRY(check_workspace(CC, who, workspace, workspace_bytes, need));
+  HDF_TRY(check_aligned8(CC, who, "count", count));
+  HDF_TRY(check_aligned8(CC, who, "values", values));
+  HDF_TRY(check_aligned8(CC, who, "result", result));
+  const struct { const void* p; int64_t n; const char* name; } out[4] = {{count, capacity * 8, "count"},
+                                                                        {values, C * capacity * Q * 24, "values"},
+                                                                        {result, 32, "result"},
+                                                                        {workspace, need, "workspace"}};
+  for (int i = 0; i < 4; i++) {
+    HDF_CHECK_ARG(!hdf_overlap(out[i].p, out[i].n, ids, V * 4) && !hdf_overlap(out[i].p, out[i].n, image, C * V * 4),
+                  "components: %s: %s overlaps an input", who, out[i].name);
+    for (int j = i + 1; j < 4; j++)
+      HDF_CHECK_ARG(!hdf_overlap(out[i].p, out[i].n, out[j].p, out[j].n), "components: %s: %s overlaps %s", who, out[i].name,
+                    out[j].name);
+  }
+  return hdf_launch_cc_quantiles(ids, image, C, D, H, W, capacity, q, Q, (long long*)count, values, (unsigned long long*)result,
+                                 workspace, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------- per-lesion surface distances

@@ -1,7 +1,21 @@
 // What the per-id table kernels share (components.hip: the component table and the filter's sizes; measure.hip: the
-// region measurements): the runs of a wave, the walk of a workgroup, its LDS slots, and the integer atomics on a row.
+// region measurements; quantiles.hip: the order statistics): the runs of a wave, the walk of a workgroup, its LDS slots,
+// the integer atomics on a row, the orderable key of a float and the layout of an id's box.
 #pragma once
 #include "wave_ops.h"
+
+// ------------------------------------------------------------------------------------------------ keys and boxes
+// a float's bits as an unsigned that orders like the value; -0 is +0
+__device__ __forceinline__ uint32_t order_of(uint32_t bits) {
+  if (bits == 0x80000000u) bits = 0u;
+  return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float value_of(uint32_t order) {
+  return __uint_as_float((order >> 31) ? order ^ 0x80000000u : ~order);
+}
+// the box of an id as the walk of measure.hip leaves it: six maxima that start from 0
+constexpr int CC_BOX_COLS = 6;   // BIG - zmin, zmax, BIG - ymin, ymax, BIG - xmin, xmax
+constexpr int CC_BOX_BIG = 0x7fffffff;
 
 // ------------------------------------------------------------------------------------------------ runs
 // The lanes of a wave hold 64 consecutive voxels.  A run is a maximal stretch of lanes with the same non-zero id that

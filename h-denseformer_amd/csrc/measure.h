@@ -16,3 +16,8 @@ int64_t hdf_cc_measure_ws_bytes(int C, int64_t capacity);
 
 int hdf_launch_cc_measure(const int32_t* ids, const float* image, int C, int D, int H, int W, int64_t capacity, long long* geom,
                           double* stats, long long* pos, unsigned long long* result, void* ws, hipStream_t st);
+
+// measure_table_kernel alone: n and the coordinate sums of every id in geom [capacity][4], its box in box
+// [capacity][CC_BOX_COLS] (cc_runs.h), the four result words; with C = 0 no key is formed and image and keys may be null
+int hdf_launch_cc_measure_walk(const int32_t* ids, const float* image, int C, int H, int W, int64_t V, int64_t capacity,
+                               long long* geom, int* box, unsigned long long* keys, unsigned long long* result, hipStream_t st);

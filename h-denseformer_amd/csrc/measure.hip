@@ -25,17 +25,7 @@
 namespace {
 typedef unsigned long long u64;
 constexpr int MAXC = HDF_MEASURE_MAX_CHANNELS, NSLAB = HDF_MEASURE_SLABS;
-constexpr int BOX_COLS = 6;   // BIG - zmin, zmax, BIG - ymin, ymax, BIG - xmin, xmax: six maxima that start from 0
-constexpr int BIG = 0x7fffffff;
-
-// a float's bits as an unsigned that orders like the value; -0 is +0
-__device__ __forceinline__ uint32_t order_of(uint32_t bits) {
-  if (bits == 0x80000000u) bits = 0u;
-  return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float value_of(uint32_t order) {
-  return __uint_as_float((order >> 31) ? order ^ 0x80000000u : ~order);
-}
+constexpr int BOX_COLS = CC_BOX_COLS, BIG = CC_BOX_BIG;   // (cc_runs.h, with order_of / value_of)
 __device__ __forceinline__ u64 shfl_down_u64(u64 v, int o) {
   const uint32_t lo = __shfl_down((uint32_t)v, o, 64), hi = __shfl_down((uint32_t)(v >> 32), o, 64);
   return ((u64)hi << 32) | lo;
@@ -228,6 +218,17 @@ struct Carve {
 
 int64_t hdf_cc_measure_ws_bytes(int C, int64_t capacity) { return Carve(C, capacity).total; }
 
+// The walk alone, for the units that need n and the box of every id (quantiles.hip): with C = 0 the key loops do not run
+// and neither image nor keys is read.  geom, box and result must have been cleared on the stream.
+int hdf_launch_cc_measure_walk(const int32_t* ids, const float* image, int C, int H, int W, int64_t V, int64_t capacity,
+                               long long* geom, int* box, unsigned long long* keys, unsigned long long* result,
+                               hipStream_t stream) {
+  hipLaunchKernelGGL(measure_table_kernel, dim3((unsigned)ceil_div64(V, SPAN)), dim3(256), 0, stream, ids, image, C, H, W, V,
+                     capacity, geom, box, keys, result);
+  HDF_LAUNCH_CHECK();
+  return HDF_OK;
+}
+
 int hdf_launch_cc_measure(const int32_t* ids, const float* image, int C, int D, int H, int W, int64_t capacity, long long* geom,
                           double* stats, long long* pos, unsigned long long* result, void* ws, hipStream_t stream) {
   const Carve cv(C, capacity);
@@ -240,9 +241,7 @@ int hdf_launch_cc_measure(const int32_t* ids, const float* image, int C, int D, 
   HDF_TRY(hdf_zero_async("components", result, 32, stream));
   HDF_TRY(hdf_zero_async("components", geom, (size_t)capacity * 32, stream));
   HDF_TRY(hdf_zero_async("components", w, (size_t)cv.cleared, stream));
-  hipLaunchKernelGGL(measure_table_kernel, dim3((unsigned)ceil_div64(V, SPAN)), dim3(256), 0, stream, ids, image, C, H, W, V,
-                     capacity, geom, box, keys, result);
-  HDF_LAUNCH_CHECK();
+  HDF_TRY(hdf_launch_cc_measure_walk(ids, image, C, H, W, V, capacity, geom, box, keys, result, stream));
   const dim3 gs((unsigned)(capacity * NSLAB), (unsigned)C);   // at most 524 288 x 8
   const unsigned gf = (unsigned)ceil_div64(rows, 256);        // at most 2048
   hipLaunchKernelGGL(measure_slab_kernel<false>, gs, dim3(256), 0, stream, ids, image, H, W, V, capacity, (const long long*)geom,

@@ -12,7 +12,8 @@ _MORPHOLOGY = ("binary_dilation", "binary_erosion", "binary_opening", "binary_cl
                "fill_class_holes")
 _LESIONS = ("component_overlap", "match_components", "lesion_wise_scores")
 _DETECTION = ("extract_lesion_candidates", "match_candidates", "DetectionEvaluator")
-_REGIONS = ("region_measure", "region_stats", "pet_lesion_measures")
+_REGIONS = ("region_measure", "region_stats", "pet_lesion_measures", "region_quantiles", "region_order_stats",
+            "region_median")
 _INFERENCE = ("cal_steps", "gaussian_tables", "sliding_window_predict", "slice_predict")
 
 

@@ -83,6 +83,8 @@ _PROTOS = {
     "hdf_cc_pairs": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp]),
     "hdf_cc_measure_workspace_bytes": (_i64, [_i, _i64]),
     "hdf_cc_measure": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hdf_cc_quantiles_workspace_bytes": (_i64, [_i, _i64, _i]),
+    "hdf_cc_quantiles": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _pd, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hdf_lesion_surface_workspace_bytes": (_i64, [_vp, _i64, _i, _i, _i, _i]),
     "hdf_lesion_surface": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i64, _vp, _i64, _pd, _vp, _i64, _vp, _vp]),
     "hdf_morph_workspace_bytes": (_i64, [_i, _i, _i]),

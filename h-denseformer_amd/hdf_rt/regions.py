@@ -6,9 +6,15 @@ saw; per lesion come out MTV, SUVmax, SUVmean and TLG (pet_lesion_measures), or 
 as a confidence (region_stats).  Kernels: csrc/measure.hip; definitions and the numerical contract: include/hdf.h.  No CPU
 fallback.
 
+Rank statistics -- what scipy.ndimage.median and np.percentile per id, channel and level do on the host after a full sort of
+every component -- come from region_quantiles (device tensors), region_order_stats (one dict per id) and region_median:
+the 10th and 90th percentile, the IQR, the median SUV or ADC of a lesion.  Kernels: csrc/quantiles.hip, an exact radix
+select; entry hdf_cc_quantiles.
+
 ids: any integer numbering, a value below 0 counting as 0; image: [D, H, W] (one channel) or [C, D, H, W], C up to 8.  2-D
 inputs ([H, W] with [H, W] or [C, H, W]) are the depth-1 volume.  On a tie the position of an extremum is the smallest linear
 index -- np.argmin / np.argmax, not scipy's maximum_position, which returns the last one."""
+import ctypes
 import math
 
 import numpy as np
@@ -21,6 +27,8 @@ from ._volume import WorkspaceCache
 STAT_COLS = ("sum", "mean", "m2", "min", "max", "wz", "wy", "wx")
 # one workspace per (channels, capacity) and stream, 24 + 272 C bytes an id
 _workspaces = WorkspaceCache("hdf_cc_measure_workspace_bytes")
+# one per (channels, capacity, levels) and stream, 56 bytes an id
+_quantile_workspaces = WorkspaceCache("hdf_cc_quantiles_workspace_bytes")
 
 
 def _inputs(ids, image):
@@ -152,3 +160,67 @@ def pet_lesion_measures(ids, suv, spacing, capacity=4096):
         out.append({"id": d["id"], "size": d["size"], "MTV": mtv, "SUVmax": ch["max"], "SUVmean": ch["mean"],
                     "TLG": ch["mean"] * mtv, "SUVpeak_at": ch["argmax"]})
     return out
+
+
+def _device_inputs(ids, image):
+    """_inputs for the order statistics, which take device tensors only: they exist to spare the copies, so a host array
+    is a mistake of the caller's, not something to upload quietly"""
+    for name, a in (("ids", ids), ("image", image)):
+        if not (torch.is_tensor(a) and a.is_cuda):
+            raise ValueError(f"{name} must be a tensor on the GPU, got {type(a).__name__}"
+                             + (f" on {a.device}" if torch.is_tensor(a) else ""))
+    if ids.device != image.device:
+        raise ValueError(f"ids on {ids.device}, image on {image.device}")
+    return _inputs(ids, image)
+
+
+def _levels(q):
+    levels = [float(v) for v in (q if isinstance(q, (tuple, list, np.ndarray)) else (q,))]
+    return levels, (ctypes.c_double * max(len(levels), 1))(*levels)
+
+
+def region_quantiles(ids, image, q=(0.5,), capacity=4096):
+    """(count int64 [capacity], values fp64 [C, capacity, Q, 3], result int64 [4]) on the device; nothing waits on the host.
+    q: levels in [0, 1], in any order (0.5 the median, 0 the minimum, 1 the maximum).  Row id-1: count = n; values, per
+    channel and level = s_lo, s_hi and s_lo + frac (s_hi - s_lo), with s the sorted values of the id, h = q (n - 1),
+    lo = floor(h), frac = h - lo and hi = lo + (frac > 0): np.quantile's default, the linear interpolation.  result as
+    region_measure's.  Ids above capacity are left out; a row no voxel holds is zeros.  Exact order statistics: every output is
+    the same in every bit from call to call.  ids and image must be device tensors, otherwise shaped as region_measure
+    takes them."""
+    ids, image = _device_inputs(ids, image)
+    Cn, (D, H, W) = int(image.shape[0]), (int(s) for s in ids.shape)
+    capacity = int(capacity)
+    rows = max(capacity, 0)
+    levels, host_q = _levels(q)
+    Q = len(levels)
+    with torch.cuda.device(ids.device):
+        ws = _quantile_workspaces.workspace(ids.device, Cn, capacity, Q)
+        count = torch.empty((rows,), dtype=torch.int64, device=ids.device)
+        values = torch.empty((Cn, rows, Q, 3), dtype=torch.float64, device=ids.device)
+        res = torch.empty(4, dtype=torch.int64, device=ids.device)
+        check(lib().hdf_cc_quantiles(ptr(ids), ptr(image), Cn, D, H, W, capacity, host_q, Q, ptr(count), ptr(values), ptr(res),
+                                     ptr(ws), ws.numel(), stream_ptr()), "hdf_cc_quantiles")
+    return count, values, res
+
+
+def region_order_stats(ids, image, q=(0.1, 0.5, 0.9), capacity=4096):
+    """quantiles, ONE copy to the host: a list with a dict per id that is present, in id order -- id, size and channels, a
+    list with a dict per channel: quantiles (the interpolated values in the order of q), lower and upper (the order
+    statistics s_lo and s_hi they were formed from).  An id above `capacity` is an HdfError."""
+    count, values, res = region_quantiles(ids, image, q, capacity)
+    Cn, cap, Q = (int(s) for s in values.shape[:3])
+    host = torch.cat([res, count, values.view(torch.int64).reshape(-1)]).cpu().numpy()
+    if int(host[0]) > cap:
+        raise _lib.HdfError(f"region_order_stats: ids up to {int(host[0])}, capacity {cap}")
+    n = host[4: 4 + cap]
+    v = host[4 + cap:].view(np.float64).reshape(Cn, cap, Q, 3)
+    return [{"id": row + 1, "size": int(n[row]),
+             "channels": [{"quantiles": v[c, row, :, 2].tolist(), "lower": v[c, row, :, 0].tolist(),
+                           "upper": v[c, row, :, 1].tolist()} for c in range(Cn)]}
+            for row in np.flatnonzero(n > 0).tolist()]
+
+
+def region_median(ids, image, capacity=4096):
+    """fp64 [C, capacity] on the device: the median of every id in every channel (the mean of the two middle values where
+    the id has an even number of voxels), 0 for an id no voxel holds"""
+    return region_quantiles(ids, image, (0.5,), capacity)[1][:, :, 0, 2]

@@ -483,6 +483,43 @@ int hdf_cc_measure(const int32_t* ids, const float* image /* [C][D][H][W] */, in
                    int64_t* geom /* [capacity][4] */, double* stats /* [C][capacity][8] */, int64_t* pos /* [C][capacity][2] */,
                    uint64_t* result /* [4] */, void* workspace, int64_t workspace_bytes, hdf_stream stream);
 
+/* ---- order statistics of an image under an id map: the median and the percentiles of every id, what scipy.ndimage.median
+ * or np.percentile give per id, channel and level on the host after a full sort of every component (the reference has no
+ * such code).  ids and image are as hdf_cc_measure takes them: any non-negative numbering, a value below 0 counts as 0, ids
+ * above `capacity` count only in result[0] and result[1].  q: a HOST pointer to Q levels, each in [0, 1], in any order,
+ * duplicates allowed; it is read before the call returns.
+ * The definition.  For an id with n voxels let s_0 <= ... <= s_{n-1} be its values in channel c, a -0 read as +0, and take a
+ * level q.  Then h = fl(q * (double)(n - 1)), one fp64 multiplication; lo = floor(h); frac = h - lo, which is exact;
+ * hi = lo + (frac > 0).
+ *   count    int64 [capacity], row id-1 = n.
+ *   values   fp64 [C][capacity][Q][3], row id-1 of channel c, level k = (double)s_lo, (double)s_hi -- each an fp32 value
+ *            widened -- and fl(s_lo + fl(frac * fl(s_hi - s_lo))): three fp64 roundings in that order, never a fused
+ *            multiply-add.  q = 0 gives the minimum and q = 1 the maximum, the min and max of hdf_cc_measure in every bit;
+ *            q = 0.5 gives the median (the mean of the two middle values where n is even).
+ *   result   [4] uint64 = the four words of hdf_cc_measure.
+ * A row whose id no voxel holds is all zero bytes in every output.  A NaN or an infinity in a component is the caller's
+ * error: that component's values are unspecified, no other row changes, nothing faults (the only address formed from a
+ * value of the image is a counter index of 8 bits).
+ * The numerical contract.  s_lo and s_hi are exact order statistics: an exact radix select (csrc/quantiles.hip) on the
+ * 32-bit key order(x) of hdf_cc_measure, four rounds of 8 bits from the top, integer counts only.  Every output is
+ * therefore the same in every bit from call to call, for every capacity >= the row's id, whatever the workspace held, and
+ * a level's row does not depend on the other levels of the call.
+ * The work: the walk of hdf_cc_measure over the id map (the image is not read there), then one workgroup per (id, channel)
+ * that reads the id's box four times -- the summed box volumes times 4 C, not the volume; a component whose box is the
+ * whole volume is served by one workgroup.  No kernel waits on another workgroup and every loop is bounded by the box.
+ * All pointers but q are device memory, the kernels are ordered on `stream`, nothing waits on the host, and a workspace may
+ * be reused by the next call on the same stream without clearing.  Refused (HDF_ERR_ARG, message "components: quantiles:
+ * ...") before anything is launched: everything hdf_cc_measure refuses -- C outside 1..8, a dimension outside 1..1024,
+ * capacity outside 1..65536, a null pointer, a workspace below hdf_cc_quantiles_workspace_bytes(C, capacity, Q) (56 bytes an
+ * id; -1 for a refused C, capacity or Q) or not aligned to 8 bytes, count, values or result not aligned to 8 bytes, any
+ * output or the workspace overlapping an input or each other -- and Q outside 1..16, a null q, a level that is NaN or
+ * outside [0, 1]. */
+int64_t hdf_cc_quantiles_workspace_bytes(int C, int64_t capacity, int Q);
+int hdf_cc_quantiles(const int32_t* ids, const float* image /* [C][D][H][W] */, int C, int D, int H, int W, int64_t capacity,
+                     const double* q /* HOST, [Q] */, int Q, int64_t* count /* [capacity] */,
+                     double* values /* [C][capacity][Q][3] */, uint64_t* result /* [4] */, void* workspace,
+                     int64_t workspace_bytes, hdf_stream stream);
+
 /* ---- per-lesion surface distances: the second number of the BraTS-2023 lesion-wise protocol (the reference has no such
  * code: its users build two full-volume masks per truth lesion on the host and hand them to SimpleITK or scipy).  For row
  * i of `lesions`, with truth id j,
