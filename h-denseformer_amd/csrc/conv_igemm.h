@@ -108,7 +108,7 @@ bool hdf_convt_fused_rows(int row_bytes);                      // row widths con
 bool hdf_convt_fused_takes(int dtype, const ConvArgs& a);      // mode 2, 3-D and depth-1 (2-D) tensors
 int hdf_launch_convt_fused(int dtype, const ConvArgs& a, hipStream_t st);
 
-// ---- conv_wr.hip: weights-in-registers form of the mode-0 launches with 64- / 128-byte rows at >= 48^3 (16-bit storage)
+// ---- conv_wr.hip: weights-in-registers form of the mode-0 launches with 128-byte rows at >= 48^3 (16-bit storage, no input transform)
 bool hdf_conv_wr_can(int dtype, const ConvArgs& a);    // the kernel handles this launch
 bool hdf_conv_wr_takes(int dtype, const ConvArgs& a);  // ... and the plan routes it there
 int hdf_launch_conv_wr(int dtype, const ConvArgs& a, hipStream_t st);

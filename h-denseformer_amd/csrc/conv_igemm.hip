@@ -429,6 +429,10 @@ __global__ __launch_bounds__(256) void conv_ws2_kernel(ConvArgs a) {
   }
   const int bswz = (r / RP256) & (CPR - 1);
 
+  // (This kernel keeps its OWN COPY of the schedule that conv_wgrad2_kernel and conv_wr_kernel take from
+  // conv_schedule.h (WsSchedule): through the header five of its forms spilled one or two more scalar registers, under
+  // every spelling of the header that was tried.  A change of the schedule is made there AND here;
+  // tests/test_gpu_tile_schedule.py holds both to the same results.)
   // Tile schedule: every workgroup first runs a contiguous share of the INTERIOR tiles (halo box inside the volume:
   // no bounds logic, one long run inside the hot copy of the phase), then a share of the
   // BORDER tiles with the checked copy.  Walking all tiles in raster order switched between the copies at every

@@ -1,10 +1,13 @@
 // Pieces shared by the convolution kernels: the MFMA wrapper per storage type, the generic halo-box staging (PITCH,
 // stage_box), the MFMA-row -> tile-voxel map of the 4x8x8 tile family, the LDS-only workgroup barrier, the persistent
-// kernels' tile record, the zero line of the LDS-DMA kernels and the phase stamps of a -DWS_DBG_STAMPS build.
+// kernels' tile record and schedule (conv_schedule.h, included here), the zero line of the LDS-DMA kernels and the phase
+// stamps of a -DWS_DBG_STAMPS build.
 // Users: conv_igemm.hip, conv_s2.hip and, through conv_wgrad_tile.h, conv_wgrad.hip (stage_box, Mma, WS_BARRIER),
-// conv_wgrad2.hip (Mma, WS_BARRIER, WsTile, the stamps) and conv_wgrad_s2.hip (Mma, WS_BARRIER, the zero line); conv_wr.hip
-// and conv_first.hip (Mma, the row maps, WS_BARRIER, WsTile).
+// conv_wgrad2.hip (Mma, WS_BARRIER, WsTile, WsSchedule, the stamps) and conv_wgrad_s2.hip (Mma, WS_BARRIER, the zero line);
+// conv_wr.hip (Mma, the row maps, WS_BARRIER, WsTile, WsSchedule, the zero line) and conv_first.hip (Mma, the row maps,
+// WS_BARRIER, WsTile).
 #pragma once
+#include "conv_schedule.h"
 #include "hdf_common.h"
 
 namespace {
@@ -123,11 +126,6 @@ __device__ __forceinline__ void ws_row_to_zx(int r, int& dz, int& x) {
     __builtin_amdgcn_s_barrier();                        \
     asm volatile("" ::: "memory");                       \
   } while (0)
-
-struct WsTile {
-  int n, z0, y0, x0, tile;
-  int k;  // index in the list the tile came from (border pass)
-};
 
 // 16 zero bytes: the source of LDS-DMA slots that lie outside the tensor (zero padding)
 __device__ __attribute__((aligned(16))) uint32_t g_zero_line[4] = {0u, 0u, 0u, 0u};

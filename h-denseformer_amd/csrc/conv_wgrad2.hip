@@ -95,82 +95,8 @@ __global__ __launch_bounds__(256) void conv_wgrad2_kernel(WgradArgs a) {
   const T* const s_src = s_safe + scb * 32 + part * EPC;
   const T* const l_src = l_safe + lcb * 32 + part * EPC;
 
-  // Tile schedule (as in conv_ws2_kernel, conv_igemm.hip): an interior pass (unchecked copy of the phase, one long run) and
-  // a border pass (checked copy); inside each, XCD x owns the x-th eighth of the raster-ordered list and its
-  // gridDim.x/8 workgroups walk it interleaved, so neighbouring tiles' halos meet in that XCD's L2.
-  const bool has_int = chan_all && ntz >= 3 && nty >= 3 && ntx >= 3;
-  const int ipz = ntz - 2, ipy = nty - 2, ipx = ntx - 2;
-  const int n_int = has_int ? a.N * ipz * ipy * ipx : 0;
-  const int per_bor = ntz * nty * ntx - (has_int ? ipz * ipy * ipx : 0);
-  const int n_bor = a.N * per_bor;
-  const int G = gridDim.x;
-  const int NX = (G % 8 == 0) ? 8 : 1;
-  const int WPX = G / NX;
-  const int xcd = blockIdx.x % NX, slot = blockIdx.x / NX;
-  auto split = [&](int total, int& begin, int& cnt) {
-    const int r0 = (int)((int64_t)total * xcd / NX), r1 = (int)((int64_t)total * (xcd + 1) / NX);
-    begin = r0 + slot;
-    cnt = (r1 - r0 > slot) ? (r1 - r0 - slot + WPX - 1) / WPX : 0;
-  };
-  int int_begin, int_cnt, bor_begin, bor_cnt;
-  split(n_int, int_begin, int_cnt);
-  split(n_bor, bor_begin, bor_cnt);
-  int sdx = 0, sdy = 0, sdz = 0, sdn = 0;  // mixed-radix digits of the stride WPX over the interior tile grid
-  if (has_int) {
-    int t = WPX;
-    sdx = t % ipx, t /= ipx;
-    sdy = t % ipy, t /= ipy;
-    sdz = t % ipz, sdn = t / ipz;
-  }
-  auto int_init = [&](WsTile& c, int k) {
-    int t = k;
-    c.x0 = (t % ipx + 1) * TW;
-    t /= ipx;
-    c.y0 = (t % ipy + 1) * TH;
-    t /= ipy;
-    c.z0 = (t % ipz + 1) * TD;
-    c.n = t / ipz;
-    c.k = k;
-  };
-  auto int_next = [&](WsTile& c) {  // + WPX tiles in raster order of the interior grid
-    int xi = (c.x0 >> 3) - 1 + sdx, yi = (c.y0 >> 3) - 1 + sdy, zi = (c.z0 >> 2) - 1 + sdz;
-    c.n += sdn;
-    if (xi >= ipx) xi -= ipx, yi++;
-    if (yi >= ipy) yi -= ipy, zi++;
-    if (zi >= ipz) zi -= ipz, c.n++;
-    c.x0 = (xi + 1) * TW, c.y0 = (yi + 1) * TH, c.z0 = (zi + 1) * TD;
-  };
-  auto bor_init = [&](WsTile& c, int k) {
-    int tz, ty, tx;
-    c.k = k;
-    c.n = k / per_bor;
-    int rem = k - c.n * per_bor;
-    if (!has_int) {
-      tx = rem % ntx, ty = (rem / ntx) % nty, tz = rem / (ntx * nty);
-    } else {
-      const int plane = nty * ntx, ring = plane - ipy * ipx;  // border tiles of a z-plane: all of it / its rim
-      if (rem < plane) {
-        tz = 0, ty = rem / ntx, tx = rem % ntx;
-      } else if (rem - plane < ipz * ring) {
-        rem -= plane;
-        tz = 1 + rem / ring;
-        rem %= ring;
-        if (rem < ntx) {
-          ty = 0, tx = rem;
-        } else if (rem - ntx < 2 * ipy) {
-          rem -= ntx;
-          ty = 1 + (rem >> 1), tx = (rem & 1) ? ntx - 1 : 0;
-        } else {
-          ty = nty - 1, tx = rem - ntx - 2 * ipy;
-        }
-      } else {
-        rem -= plane + ipz * ring;
-        tz = ntz - 1, ty = rem / ntx, tx = rem % ntx;
-      }
-    }
-    c.z0 = tz * TD, c.y0 = ty * TH, c.x0 = tx * TW;
-  };
-  auto bor_next = [&](WsTile& c) { bor_init(c, c.k + WPX); };
+  // tile schedule (conv_schedule.h): interior pass, then border pass; ragged channel blocks run every tile checked
+  const WsSchedule<TD, TH, TW> sch(a.N, ntz, nty, ntx, chan_all, (int)gridDim.x, (int)blockIdx.x);
   auto s_org_of = [&](const WsTile& c) -> const T* {
     return s_src + ((((int64_t)c.n * a.Ds + c.z0) * a.Hs + c.y0) * a.Ws + c.x0) * a.sm_pitch;
   };
@@ -306,14 +232,14 @@ __global__ __launch_bounds__(256) void conv_wgrad2_kernel(WgradArgs a) {
       constexpr bool BORDER = decltype(border_tag)::value;
       auto next = [&](WsTile& c) {
         if constexpr (BORDER)
-          bor_next(c);
+          sch.bor_next(c);
         else
-          int_next(c);
+          sch.int_next(c);
       };
       if constexpr (BORDER)
-        bor_init(T0, k);
+        sch.bor_init(T0, k);
       else
-        int_init(T0, k);
+        sch.int_init(T0, k);
       left = count - 1;
       T1 = T0;
       next(T1);
@@ -417,24 +343,24 @@ __global__ __launch_bounds__(256) void conv_wgrad2_kernel(WgradArgs a) {
       lo1 = lo2;
       ty1 = ty2, to1 = to2;
       if constexpr (BORDER)
-        bor_next(T2);
+        sch.bor_next(T2);
       else
-        int_next(T2);
+        sch.int_next(T2);
       v2 = left >= 2;
       so2 = v2 ? s_org_of(T2) : s_safe;
       lo2 = v2 ? l_org_of(T2) : l_safe;
       ty2 = ap_ty_of(T2, v2), to2 = ap_to_of(T2, v2);
     };
-    if (int_cnt > 0) {  // interior pass: the unchecked copy, one run (its own back edge: nothing drained per tile)
-      begin_pass(std::false_type{}, int_begin, int_cnt);
+    if (sch.int_cnt > 0) {  // interior pass: the unchecked copy, one run (its own back edge: nothing drained per tile)
+      begin_pass(std::false_type{}, sch.int_begin, sch.int_cnt);
       more = true;
       while (more) {
         tile_phase(std::true_type{});
         step(std::false_type{});
       }
     }
-    if (bor_cnt > 0) {  // border pass: the checked copy
-      begin_pass(std::true_type{}, bor_begin, bor_cnt);
+    if (sch.bor_cnt > 0) {  // border pass: the checked copy
+      begin_pass(std::true_type{}, sch.bor_begin, sch.bor_cnt);
       more = true;
       while (more) {
         tile_phase(std::false_type{});

@@ -44,7 +44,7 @@ def test_the_library_holds_the_expected_kernel_families(ks):
         assert "in_bwd_reduce4_kernel<%s>" % T in ks and "in_bwd_apply4_kernel<%s>" % T in ks
     assert not any(n.startswith(("in_bwd_reduce_kernel", "in_bwd_apply_kernel")) for n in ks)
     assert sorted(n for n in ks if n.startswith("conv_wr_kernel")) == [
-        "conv_wr_kernel<bf16_t, 128, 1, 2, 4, false>", "conv_wr_kernel<f16_t, 128, 1, 2, 4, false>"]
+        "conv_wr_kernel<bf16_t>", "conv_wr_kernel<f16_t>"]
 
 
 @pytest.mark.parametrize("family", NO_SCRATCH)
@@ -125,7 +125,7 @@ def test_conv_wr_routed_instantiation_keeps_scratch_out_of_the_tile_phase(ks, T)
     """the instantiation the plan routes (hdf_conv_wr_takes: 128-byte rows, K split, no transform).  Its 216-MFMA tile
     phases must stay free of scratch traffic (a scratch reload is an s_waitcnt vmcnt(0): it drains the LDS-DMA prefetch
     queue), its spills must not grow, and the hand-counted vmcnt structure must be the one the source was written for."""
-    k = ks["conv_wr_kernel<%s, 128, 1, 2, 4, false>" % T]
+    k = ks["conv_wr_kernel<%s>" % T]
     assert k["vgpr_spill_count"] <= 196 and k["private_segment_fixed_size"] <= 404, k
     ins = codeobj.disassemble(k["mangled"])
     assert len(ins) > 10000

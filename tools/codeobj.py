@@ -4,7 +4,10 @@ libhdf_hip.so carries one clang offload bundle per translation unit in .hip_fatb
 NT_AMDGPU_METADATA note lists, per kernel: registers, spills, scratch (private segment) and static LDS.
 `kernels(so)` returns {demangled name: record}; `disassemble(so, name_substring)` the instruction mnemonics of one kernel.
 CLI: python tools/codeobj.py [regex]        -> one line per kernel
-     python tools/codeobj.py --diff A.so B.so -> what a refactor changed between two builds (exit status 1 if anything)."""
+     python tools/codeobj.py --diff A.so B.so [--rename 'OLD_REGEX=NEW' ...]
+                                              -> what a refactor changed between two builds (exit status 1 if anything);
+                                                 --rename pairs a kernel of A with the kernel of B that carries its new name."""
+import collections
 import os
 import re
 import struct
@@ -129,40 +132,66 @@ def instruction_streams(so=LIB):
     return out
 
 
-def diff(so_a, so_b):
-    """print the differences between two builds; returns their number"""
+def _mnemonic_counts(lines):
+    """{mnemonic: count}; an s_waitcnt counts per operand string (hand-counted vmcnt waits are part of a kernel's design)"""
+    c = collections.Counter()
+    for l in lines:
+        c[l if l.startswith("s_waitcnt") else l.split(" ")[0]] += 1
+    return c
+
+
+def diff(so_a, so_b, renames=()):
+    """print the differences between two builds; returns their number.  renames: (regex, replacement) pairs applied to the
+    demangled kernel names of A -- a kernel whose name changes that way is compared with B's kernel of the new name"""
     ka = {k["mangled"]: k for k in kernels(so_a).values()}
     kb = {k["mangled"]: k for k in kernels(so_b).values()}
+    b_by_name = {k["name"]: m for m, k in kb.items()}
+    pairs = {}  # mangled name in A -> mangled name in B
+    for m, k in ka.items():
+        new = k["name"]
+        for pat, rep in renames:
+            new = re.sub(pat, rep, new)
+        mb = b_by_name.get(new) if new != k["name"] else (m if m in kb else None)
+        if mb is not None:
+            pairs[m] = mb
     n = 0
-    for tag, only in (("only in A", sorted(set(ka) - set(kb))), ("only in B", sorted(set(kb) - set(ka)))):
+    for tag, recs, only in (("only in A", ka, sorted(set(ka) - set(pairs))),
+                            ("only in B", kb, sorted(set(kb) - set(pairs.values())))):
         for m in only:
-            print("%s: %s" % (tag, (ka.get(m) or kb[m])["name"]))
+            print("%s: %s" % (tag, recs[m]["name"]))
             n += 1
-    common = sorted(set(ka) & set(kb))
     sa, sb = instruction_streams(so_a), instruction_streams(so_b)
-    for tag, streams in (("A", sa), ("B", sb)):
-        missing = [m for m in common if not streams.get(m)]
+    for tag, streams, names in (("A", sa, pairs), ("B", sb, pairs.values())):
+        missing = [m for m in names if not streams.get(m)]
         if missing:
             raise RuntimeError("no instruction stream in %s for %d kernels, e.g. %s" % (tag, len(missing), missing[0]))
-    for m in common:
-        ra, rb = [ka[m].get(r, 0) for r in RESOURCES], [kb[m].get(r, 0) for r in RESOURCES]
+    for m, mb in sorted(pairs.items()):
+        ra, rb = [ka[m].get(r, 0) for r in RESOURCES], [kb[mb].get(r, 0) for r in RESOURCES]
         if ra != rb:
             print("resources differ: %s\n    %s" % (ka[m]["name"], ", ".join(
                 "%s %d -> %d" % (r, x, y) for r, x, y in zip(RESOURCES, ra, rb) if x != y)))
             n += 1
-        if sa[m] != sb[m]:
-            la, lb = sa[m], sb[m]
+        if sa[m] != sb[mb]:
+            la, lb = sa[m], sb[mb]
             first = next((i for i, (x, y) in enumerate(zip(la, lb)) if x != y), min(len(la), len(lb)))
             print("instructions differ: %s\n    %d -> %d instructions, first difference at %d: %s | %s" % (
                 ka[m]["name"], len(la), len(lb), first, la[first] if first < len(la) else "-", lb[first] if first < len(lb) else "-"))
+            ca, cb = _mnemonic_counts(la), _mnemonic_counts(lb)
+            moved = ["%s %+d" % (k, cb[k] - ca[k]) for k in sorted(set(ca) | set(cb)) if ca[k] != cb[k]]
+            print("    counts moved: %s" % (", ".join(moved) or "none (order or operands only)"))
             n += 1
-    print("%d kernels in A, %d in B, %d common, %d differences" % (len(ka), len(kb), len(common), n))
+    print("%d kernels in A, %d in B, %d paired, %d differences" % (len(ka), len(kb), len(pairs), n))
     return n
 
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--diff":
-        sys.exit(1 if diff(sys.argv[2], sys.argv[3]) else 0)
+        args, renames = sys.argv[2:], []
+        while "--rename" in args:
+            i = args.index("--rename")
+            renames.append(tuple(args[i + 1].split("=", 1)))
+            del args[i:i + 2]
+        sys.exit(1 if diff(args[0], args[1], renames) else 0)
     pat = sys.argv[1] if len(sys.argv) > 1 else ""
     for n, k in sorted(kernels().items()):
         if pat and not re.search(pat, n):

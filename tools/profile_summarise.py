@@ -192,7 +192,7 @@ if fe and wr:
     fk, nf = per_launch(fe, "FETCH_SIZE")
     wk, nw = per_launch(wr, "WRITE_SIZE")
     rec = {
-        "kernel": "conv_wr_kernel<bf16_t, 128, 1, 2, 4, false> (block_1_1_right forward: 64->32 channels @128^3, batch 2)",
+        "kernel": "conv_wr_kernel<bf16_t> (block_1_1_right forward: 64->32 channels @128^3, batch 2)",
         "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, in a separate pass, --pmc WRITE_SIZE) --output-format "
                    "csv -- python3 tools/conv_micro.py --cin 64 --cout 32 --xf 0 --reps 2",
         "launches_averaged": [nf, nw], "FETCH_SIZE_KB_raw": fk, "WRITE_SIZE_KB": wk,
